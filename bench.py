@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark: simulated-connectivity verdict grid on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config config3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config config3] [--dump-outputs DIR] [--full]
+
+A plain run prepares the workload, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, the workload's shape and the preparation times).  --full adds everything that takes
+runs of its own: the per-phase HIP-event times and the emit's roofline, the fill ceiling, the table
+read-back, the assembled table of an N > 1 run and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step left in the output buffers (see dump_outputs).
 
 A step is one full pass of the hot path over the synthetic workload with every input table
 already resident in HBM: selector evaluation, peer rows, port tables, target membership and
@@ -96,6 +102,38 @@ def cpu_baseline(data, seconds: float, seed: int = 1):
     }
 
 
+DUMP_SEED = 20250217
+DUMP_WORDS = 1 << 16  # sampled 64-bit words per plane: 65536 x 64 float32 bits = 16 MiB a plane
+DUMP_STATUS = 1 << 22  # status bytes written whole up to this many (16 MiB as float32), sampled above
+
+
+def dump_outputs(out_dir, d_in, d_eg, d_st, suffix=""):
+    """Write the step's outputs (the buffers a caller of run_device / run_blocks_device passes and
+    reads) as float32 .npy files: `ingress_bits` / `egress_bits`, the verdict bits of a fixed, seeded
+    sample of each packed plane's 64-bit words ([words][64], bit b of word i at [i][b], words in
+    ascending buffer order; a plane of at most DUMP_WORDS words is written whole), and `status`, the
+    job-status bytes.  The sample depends on the buffer's length only, so two builds running the same
+    arguments write the same cells."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(flat, limit, seed):
+        n = flat.numel()
+        if n > limit:
+            idx = np.sort(np.random.default_rng(seed).choice(n, size=limit, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.cpu().numpy()
+
+    for k, (name, plane) in enumerate((("ingress_bits", d_in), ("egress_bits", d_eg))):
+        words = np.ascontiguousarray(sample(plane.reshape(-1), DUMP_WORDS, DUMP_SEED + k)).view(np.uint8).reshape(-1, 8)
+        bits = np.unpackbits(words, axis=1, bitorder="little")  # (little-endian host: byte j holds bits 8j..8j+7)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), bits.astype(np.float32))
+    st = sample(d_st.reshape(-1), DUMP_STATUS, DUMP_SEED + 2)
+    np.save(os.path.join(out_dir, f"status{suffix}.npy"), st.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -103,8 +141,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)  # GPU clocks settle after the host-side prepare
     ap.add_argument("--config", default="config3", choices=["config2", "config3", "config4", "config5", "config3u"])
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-assemble", action="store_true", help="skip the N>1 all-gather timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle timing")
+    ap.add_argument("--no-assemble", action="store_true", help="with --full: skip the N>1 all-gather timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-phase times and the emit roofline, fill "
+                         "ceiling, table read-back, the N>1 assembled table, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; see dump_outputs)")
     ap.add_argument("--partition", default="source", choices=["source", "target"],
                     help="row partition across ranks (include/cyclonus_hip.h cyc_rows; the same at N=1)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
@@ -201,6 +244,9 @@ def main():
         def step():
             eng.run_device(d_in.data_ptr(), d_eg.data_ptr(), d_st.data_ptr(), stream, lo, hi, part)
 
+    if args.dump_outputs:  # words no kernel writes (allocation padding) read the same in every run
+        for t in (d_in, d_eg, d_st):
+            t.zero_()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -216,6 +262,62 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    status = d_st.cpu().numpy()
+    if bt is not None:  # the cells of each batched problem (the slabs hold nothing else)
+        cells = bt.cells(status)
+        if world > 1:
+            ct = torch.tensor([cells], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(ct)
+            cells = int(ct.item())
+    else:
+        valid_slots = int((status == 1).sum())  # (dst, slot) pairs with a VALID job
+        cells = P * valid_slots  # every source pod x every valid (dst, slot) job
+    ms_per_step = dt / args.steps * 1e3
+    value = cells / (dt / args.steps)
+    classes_in, classes_eg = eng.classes()
+
+    if args.dump_outputs:  # before anything below runs further steps or fills the planes
+        dump_outputs(args.dump_outputs, d_in, d_eg, d_st, f"_rank{rank}" if world > 1 else "")
+
+    line = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "verdicts/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (cyclonus_amd/generator.py restated generate sweep)" if args.config == "config5" else "synthetic (cyclonus_amd/synth.py, xoshiro256** seed 20250217)",
+        "config": {
+            "workload": f"{data['name']}: {data['description']}",
+            "pods": P,
+            "policies": len(data["policies"]),
+            "slots": K,
+            "cells": cells,
+            "targets_in": shape["targets_in"],
+            "targets_eg": shape["targets_eg"],
+            "peers": shape["peers"],
+            "identities_in": shape["classes_in"],
+            "identities_eg": shape["classes_eg"],
+            "classes_in": classes_in,
+            "classes_eg": classes_eg,
+            "parallelism": f"{part}-row shards x{world}",
+            "partition": part,
+            "rows_per_rank": rows,
+        },
+        "prepare_s": prepare_s,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # assembled table (not part of `value`): RCCL all-gather of both planes' row shards into the
     # full table on every rank, timed separately (max over ranks)
@@ -308,7 +410,6 @@ def main():
     eng.set_option("graphs", graphs)
     tm = np.array(tm)
     pipe_ms, emit_ms, rows_ms = (float(x) for x in tm.mean(axis=0))
-    classes_in, classes_eg = eng.classes()
 
     # practical write ceiling for the same bytes: torch's fill kernel over both output planes
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -348,19 +449,6 @@ def main():
         del host
     except Exception as e:  # informational
         readback = {"error": f"{type(e).__name__}: {e}"}
-
-    status = d_st.cpu().numpy()
-    if bt is not None:  # the cells of each batched problem (the slabs hold nothing else)
-        cells = bt.cells(status)
-        if world > 1:
-            ct = torch.tensor([cells], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-            dist.all_reduce(ct)
-            cells = int(ct.item())
-    else:
-        valid_slots = int((status == 1).sum())  # (dst, slot) pairs with a VALID job
-        cells = P * valid_slots  # every source pod x every valid (dst, slot) job
-    ms_per_step = dt / args.steps * 1e3
-    value = cells / (dt / args.steps)
 
     # the emit writes each plane (ingress, egress) of this rank's rows once, both in ONE launch:
     # rows x K x W x 8 B per plane = 2 bits per cell — less the rows that already hold their class
@@ -407,36 +495,7 @@ def main():
                     "note": "no GEMM-shaped step on this path (DESIGN.md section 4): measured, not assumed"}
 
     if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "verdicts/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic (cyclonus_amd/generator.py restated generate sweep)" if args.config == "config5" else "synthetic (cyclonus_amd/synth.py, xoshiro256** seed 20250217)",
-            "config": {
-                "workload": f"{data['name']}: {data['description']}",
-                "pods": P,
-                "policies": len(data["policies"]),
-                "slots": K,
-                "cells": cells,
-                "targets_in": shape["targets_in"],
-                "targets_eg": shape["targets_eg"],
-                "peers": shape["peers"],
-                "identities_in": shape["classes_in"],
-                "identities_eg": shape["classes_eg"],
-                "classes_in": classes_in,
-                "classes_eg": classes_eg,
-                "parallelism": f"{part}-row shards x{world}",
-                "partition": part,
-                "rows_per_rank": rows,
-            },
+        line.update({
             "roofline": {
                 "bound": "hbm",
                 "kernel": emit_kernel,
@@ -456,10 +515,9 @@ def main():
                 "mfma": mfma,
             },
             "launch": launch_desc,
-            "prepare_s": prepare_s,
             "readback": readback,
             "pipeline_ms": {"total": pipe_ms, "emit": emit_ms, "class_rows": rows_ms, "front": pipe_ms - emit_ms - rows_ms},
-        }
+        })
         if assembled is not None:
             if "all_gather_ms" in assembled:  # whole-table-on-every-rank throughput
                 assembled["value"] = cells / (dt / args.steps + assembled.get("whole_table_ms", assembled["all_gather_ms"]) * 1e-3)

@@ -6,7 +6,7 @@ i=0
 for spec in "$@"; do
   i=$((i+1)); args=""
   for o in $spec; do args="$args --opt $o"; done
-  timeout -k 10 300 python -u bench.py --config $CFG --no-cpu-baseline --steps 30 --warmup 10 $args > $OUT/opt_${CFG}_${i}_$rep.log 2>&1
+  timeout -k 10 300 python -u bench.py --full --config $CFG --no-cpu-baseline --steps 30 --warmup 10 $args > $OUT/opt_${CFG}_${i}_$rep.log 2>&1
   echo "$i: $spec" > $OUT/opt_${CFG}_${i}.spec
 done
 done

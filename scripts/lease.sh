@@ -4,7 +4,7 @@
 # steps:
 #   tests [pytest args]        GPU test suite (-m gpu; K=a+or+b selects -k "a or b")
 #   smoke                      __graft_entry__.smoke()
-#   bench CFG [args]           python bench.py --config CFG [args]       -> bench_CFG[_TAG].log
+#   bench CFG [args]           python bench.py --full --config CFG [args] -> bench_CFG[_TAG].log
 #   prof CFG                   bench line, rocprofv3 --kernel-trace --stats of the bench command,
 #                              FETCH_SIZE / WRITE_SIZE / MFMA PMC passes over eager steps
 #   ks CFG N [NAME=V ...]      kernel stats of N eager steps (tokens CYC_SHARD=r/N, CYC_PART=source|target)
@@ -13,7 +13,7 @@
 #   py SCRIPT [args]           any python script under scripts/ (180 s limit)
 #   counters                   rocprofv3 -L (the counters this box's gfx950 offers)
 #   bin PROBE [args]           a probe built from scripts/*.hip (scripts/PROBE, 180 s limit)
-#   dist N CFG [args]          bench.py as an N-rank torch.distributed.run job on this box (tokens:
+#   dist N CFG [args]          bench.py --full as an N-rank torch.distributed.run job on this box (tokens:
 #                              CYC_BENCH_BACKEND=gloo for a one-GPU rehearsal, CYC_BENCH_FORCE_DIST=1)
 #   ab CFG SPEC...             kernel stats per library variant (scripts/ab_kernels.sh; REPS env, CYC_SHARD tokens)
 #   pmcab VARIANT...           emit PMC passes per scripts/emit_halves_ab.py variant (scripts/pmc_emit_ab.sh)
@@ -42,12 +42,12 @@ for spec in "$@"; do
       targs=(); for a in "$@"; do if [[ $a == K=* ]]; then targs+=(-k "$(echo "${a#K=}" | tr '+' ' ')"); else targs+=("$a"); fi; done
       timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --durations=40 --timeout 300 --timeout-method thread "${targs[@]}" > $OUT/gpu_tests.log 2>&1 ;;
     smoke) timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 ;;
-    bench) timeout -k 10 300 python -u bench.py --config "$@" > $OUT/bench_$tag.log 2>&1 ;;
+    bench) timeout -k 10 300 python -u bench.py --full --config "$@" > $OUT/bench_$tag.log 2>&1 ;;
     prof)
       CFG=$1
-      timeout -k 10 300 python -u bench.py --config $CFG > $OUT/bench_$CFG.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --config $CFG > $OUT/bench_$CFG.log 2>&1
       prof_env
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$CFG -o run -- python3 bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prof_$CFG.log 2>&1
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$CFG -o run -- python3 bench.py --full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prof_$CFG.log 2>&1
       timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$CFG -o fetch -- python3 scripts/profile_eager.py $CFG 5 > $OUT/pmc_fetch_$CFG.log 2>&1
       timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$CFG -o write -- python3 scripts/profile_eager.py $CFG 5 > $OUT/pmc_write_$CFG.log 2>&1
       bash scripts/pmc_mfma.sh $NAME $CFG ;;
@@ -65,7 +65,7 @@ for spec in "$@"; do
     dist)
       NP=$1; CFG=$2; shift 2
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $NP --master-addr 127.0.0.1 \
-        --master-port $((29500 + RANDOM % 400)) bench.py --gpus $NP --config $CFG "$@" > $OUT/dist_$tag.log 2>&1 ;;
+        --master-port $((29500 + RANDOM % 400)) bench.py --full --gpus $NP --config $CFG "$@" > $OUT/dist_$tag.log 2>&1 ;;
     ab) timeout -k 10 900 bash scripts/ab_kernels.sh $NAME "$@" ;;
     pmc) timeout -k 10 700 bash scripts/pmc_passes.sh $NAME "$@" ;;
     pmcab) timeout -k 10 900 bash scripts/pmc_emit_ab.sh $NAME "$@" ;;
