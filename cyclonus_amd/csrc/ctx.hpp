@@ -172,22 +172,22 @@ struct cyc_ctx {
   uint32_t n_act_ph1[2] = {0, 0};  // row phases: active identities whose first row is before the split (every
                                    // phase-1 class's representative is one of them)
   double act_targets[2] = {0, 0};  // mean namespace targets per active identity (range plan)
-  // Diagnostic path selectors (cyc_set_option; results never change, the GPU tests force each path):
+  // The path decisions in effect (route.hpp), re-resolved (reroute) whenever a fact they read changes:
+  // by prepare_device, by ensure_range and by cyc_set_option — a run only reads them.
+  Route route = resolve_route(RouteIn{});
+  // Diagnostic path selectors (cyc_set_option; results never change, the GPU tests force each path;
+  // what -1 = auto chooses: resolve_route):
   int use_graphs = -1;  // "graphs": 1 = graph replay, 2 = the same DAG enqueued eagerly on three
-                        // streams with events (no graph launch), 0 = eager on one stream with phase
-                        // events, -1 = auto: 2 when the fused front applies (its launches on one
-                        // stream start ~8 us sooner after the previous step's emit than a graph
-                        // replay: profiles/r01_front_fused_ab.txt), else 1
+                        // streams with events (no graph launch), 0 = eager on one stream with phase events
   int ip_iv = -1;       // "ip_iv": IP rows as pod intervals where the network's family is address-monotone
                         // in pod order (-1 auto = 1), 0 never
   int ip_range = -1;    // "ip_range": IP rows of few, close pods from the address index: -1 auto (where the
                         // words are not affine), 1 wherever they fit, 0 never
   int pod_rows = -1;    // "pod_rows": pod-peer PM rows per pod directly (1), through identity outcomes
-                        // and word runs (0), or -1 = direct when identities >= pods / 2
-  int member_wave = -1; // "member_wave": membership with a wave (1) or a thread (0) per identity,
-                        // -1 = auto by identity count
+                        // and word runs (0)
+  int member_wave = -1; // "member_wave": membership with a wave (1) or a thread (0) per identity
   int pod_words = -1;   // "pod_words": pod-peer words in the class rows from identity sets (1, IDO),
-                        // from materialised PM rows (0), or IDO when every word has <= IDO_MAX_RUNS runs
+                        // from materialised PM rows (0)
   int64_t class_rpb_opt = 0;  // "class_rpb": IDO class-row representatives per block; 0 = auto
                               // (profiles/r04_class_rpb_ab.txt)
   int step_events = 0;  // "step_events": graph / eager-DAG runs record the whole-step timing events (1);
@@ -196,15 +196,13 @@ struct cyc_ctx {
   int pl_wave = 1;      // "pl_wave": PM-build class rows a wave per 64-word chunk where they fit (1),
                         // or a thread per (slot chunk, word) item (0)
   int class_inplace = -1; // "class_inplace": fused-front class rows written straight into the output
-                          // planes (the first member pod's row), the emit copying only the others (1);
-                          // -1 = auto (inplace_ok)
+                          // planes (the first member pod's row), the emit copying only the others (1)
   int pr_group = -1;   // "pr_group": sparse pod-peer rows, pod peers per block (1..64; -1 = auto)
-  int sel_lazy = -1;    // "sel_lazy": selectors evaluated where used (1) or as the dense SELRES table
-                        // first (0); -1 = lazy on the fused front of PM builds
+  int sel_lazy = -1;    // "sel_lazy": selectors evaluated where used (1) or as the dense SELRES table first (0)
   int front_fused = 1;  // "front_fused": the front as block-range-fused launches on one stream
-                        // (enq_front_fused), 0 = the two-branch DAG
+                        // (build_front, launch_front), 0 = the two-branch DAG
   int emit_interleave = -1;  // "emit_interleave": a target-row emit's row list alternates the planes'
-                             // rows (1) or is [plane 0][plane 1] (0); -1 = auto (planes >= 8 GB)
+                             // rows (1) or is [plane 0][plane 1] (0)
   // what the last enqueued emit launched (cyc_last_emit): kernel name(s) and launch count
   std::string emit_kernel;
   int emit_launches = 0;
@@ -257,8 +255,8 @@ struct cyc_ctx {
   // its emit re-reads them; the whole table's (~400 MB) are not, and its emit reads them from HBM
   // between its writes (round 6, profiles/r06_emit_footprint_ab.txt).  The front before the class rows
   // runs once.
-  int row_phases = -1;     // -1 auto (whole no-panic tables of >= 8 GB planes), 1 = off, 2 = whenever possible
-  uint32_t phase_split = 0;   // the range plan's split row (0: no phases): emit lists are [rows < split][rows >= split]
+  int row_phases = -1;     // -1 auto, 1 = off, 2 = whenever possible; Route::phase_split = the range plan's split
+                           // row (0: no phases): emit lists are [rows < split][rows >= split]
   uint32_t phase_n1[2] = {0, 0};  // per plane: rows before the split in its emit list
   int phase_used = 0;      // the last run's phases (2, or 0 for a plain run)
   hipEvent_t ev_p[2] = {nullptr, nullptr};  // eager runs: around phase 2's class rows (cyc_last_timings)

@@ -3,6 +3,8 @@
 // static): included once, by engine.hip, in stage order.
 #pragma once
 
+#include "route.hpp"  // IDO_MAX_RUNS, IDO_LDS_BYTES, PL_NB
+
 namespace cyc {
 
 // Class rows.  For a class representative i, a chunk of KC job slots and one 64-pod word w, walk
@@ -108,14 +110,10 @@ __device__ __forceinline__ void ht_clear_slice(const RowArgs& a, uint32_t bid, u
   for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) a.ht_clear[i] = 0xFFFFFFFFu;
 }
 
-// Most 64-pod words hold 1-2 identity runs (pods of a deployment are contiguous); IDO builds are
-// used only when no word holds more than IDO_MAX_RUNS runs (host-checked, plan_peers).
-constexpr uint32_t IDO_MAX_RUNS = 4;
-struct WordRuns {
+struct WordRuns {  // a 64-pod word's identity runs (at most IDO_MAX_RUNS: route.hpp)
   uint32_t e[IDO_MAX_RUNS];   // egress identity of each run
   uint64_t m[IDO_MAX_RUNS];   // its pods in the word (0 = unused run)
 };
-constexpr uint32_t IDO_LDS_BYTES = 48 * 1024;  // staged identity sets per class-row block
 
 // Pod-peer outcomes packed over egress identities: one wave per (64 identities, PB_GROUP pod
 // peers): the identities' (namespace, namespace labels, labels) are loaded once and the group's
@@ -763,7 +761,7 @@ __device__ __forceinline__ void pl_items(const RowArgs& a, const PlShared& sh, c
 
 // PL_WBATCH: PM words in flight per wave-per-chunk batch (8: 78 VGPRs, config #4 class rows +7 us:
 // profiles/r03_front_b_d_ab.txt)
-constexpr uint32_t PL_WBATCH = 4, PL_NB = 4;
+constexpr uint32_t PL_WBATCH = 4;
 // An entry's lane fields for the wave-per-chunk rows: row, port bits, mask of the 64-word chunks
 // holding a nonzero PM word of it (IP rows: from the IP-row pass; other rows: all)
 struct PlLane {
@@ -810,7 +808,7 @@ __device__ __forceinline__ void pl_wave_chunks(const RowArgs& a, const PlShared&
                                                uint32_t m, bool allow_all, uint64_t lastmask, uint32_t w0, uint32_t wa) {
   static_assert(PL_LDS % 64 == 0, "a lane group of entries is all in LDS or all spilled");
   const uint32_t lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
-  // the chunks holding the window's words (<= 64 chunks in all: pl_wave_ok)
+  // the chunks holding the window's words (<= 64 chunks in all: Route::pl_wave)
   const uint32_t cend = (w0 + wa + 63) / 64;
   const PlLane g0 = pl_lane(a, sh.e, lane, m);  // entries 0..63, one per lane, for every chunk
   uint64_t* const rows = a.A + arow_of(a, i) * a.K * a.WA;  // the class row's slot 0

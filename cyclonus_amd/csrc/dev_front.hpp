@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_front_a(FrontA f) {
 // directions into segment 0: one window).
 struct FrontB {
   uint32_t nb[13];      // IP rows x2 | pod-peer rows x2 (or identity sets, segment 2) | membership in | eg | port bits |
-                        // port table | slot words (the last two: runs without launch A, enq_front_fused) |
+                        // port table | slot words (the last two: runs without launch A, build_front) |
                         // IP rows from address ranges x2 | IP rows as pod intervals x2
   uint32_t Rv[2];       // interval-built IP rows per segment (ip_rows_iv_blk)
   const DIPIv* vtests[2];

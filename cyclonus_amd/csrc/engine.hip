@@ -669,6 +669,7 @@ int cyc_set_option(cyc_ctx* c, const char* name, int64_t value) {
       c->plvt.alloc(0);
     }
     else return fail(c, CYC_ERR_ARG, "unknown option " + n);
+    reroute(c);  // (the range plan reads no option it does not invalidate above: the route alone is re-resolved)
     drop_graph(c);
     return (int)CYC_OK;
   });
@@ -693,7 +694,7 @@ int cyc_get_option(cyc_ctx* c, const char* name, int64_t* value) {
   else if (n == "row_phases_active") *value = c->phase_used;  // (the last run's phases; 0: a plain run)
   else if (n == "class_inplace_active") {
     if (!c->prepared || c->order_lo < 0) return fail(c, CYC_ERR_ARG, "class_inplace_active: run a probe first");
-    *value = inplace_ok(c, reinterpret_cast<const uint64_t*>(16), reinterpret_cast<const uint64_t*>(16)) ? 1 : 0;
+    *value = c->route.inplace ? 1 : 0;
   }
   else if (n == "step_events") *value = c->step_events;
   else if (n == "emit_interleave") *value = c->emit_interleave;
@@ -702,12 +703,12 @@ int cyc_get_option(cyc_ctx* c, const char* name, int64_t* value) {
   else if (n == "plvt_active") *value = c->plvt_ready ? 1 : 0;
   else if (n == "pl_wave_active") {
     if (!c->prepared) return fail(c, CYC_ERR_ARG, "pl_wave_active: call cyc_probe_prepare first");
-    *value = !ido_mode(c) && pl_wave_ok(c) ? 1 : 0;
-  } else if (n == "launch") *value = c->use_graphs >= 0 ? c->use_graphs : (front_fused_ok(c) ? 2 : 1);  // in effect
-  else if (n == "front_fused_active") *value = front_fused_ok(c) ? 1 : 0;
+    *value = c->route.pl_wave ? 1 : 0;
+  } else if (n == "launch") *value = c->route.launch;  // in effect
+  else if (n == "front_fused_active") *value = c->route.fused ? 1 : 0;
   else if (n == "pod_words") {
     if (!c->prepared) return fail(c, CYC_ERR_ARG, "pod_words: call cyc_probe_prepare first");
-    *value = ido_mode(c) ? 1 : 0;
+    *value = c->route.ido ? 1 : 0;
   } else return fail(c, CYC_ERR_ARG, std::string("unknown option ") + name);
   return (int)CYC_OK;
 }

@@ -7,8 +7,6 @@
 // targets, class rows and plane are disjoint from egress ones), so the two directions can run
 // as two independent branches: one direction's front hides under the other's HBM-bound emit.
 enum { COMMON_SELECTORS = 1, COMMON_PORTS = 2, COMMON_FILL = 4, COMMON_ALL = 7 };
-// Descriptor bit rows of the port table for the egress class rows (cyc_set_option "port_bits")
-static bool port_bits_on(const cyc_ctx* c) { return std::max<size_t>(c->pb.descs.size(), 1) <= 32; }
 
 static void enq_common(cyc_ctx* c, hipStream_t st, int parts = COMMON_ALL) {
   Problem& pb = c->pb;
@@ -32,7 +30,7 @@ ports:
   if (M && pb.descs.size())
     k_portok<<<grid1(uint64_t(M) * D, 256), 256, 0, st>>>(M, D, c->pms.as<DPortM>(), c->pents.as<DPortEntry>(),
                                                           c->descs.as<DDesc>(), c->portok.as<uint8_t>());
-  if (M && pb.descs.size() && port_bits_on(c))
+  if (M && pb.descs.size() && c->route.port_bits)
     k_portbits<<<(M + 255) / 256, 256, 0, st>>>(M, D, c->portok.as<uint8_t>(), c->portbits.as<uint32_t>());
   // 4. per-slot destination words
   if (uint64_t(K) * W)
@@ -40,11 +38,6 @@ ports:
         P, K, W, D, c->slot_desc.as<int32_t>(), c->slot_status.as<uint8_t>(), c->VALID.as<uint64_t>(),
         c->DESCW.as<int32_t>(), c->DM.as<uint64_t>());
 }
-
-// Pod peers folded into per-class identity sets, expanded by the class rows over each word's
-// identity runs (no PM pod rows)?  Needs: no panic possible (the panic path walks PM / ER rows in
-// peer order), few runs per word, and identity sets of bounded size.
-static bool ido_mode(const cyc_ctx* c) { return c->pod_words != 0 && c->pb.blocks.empty() && ido_possible(c); }
 
 // 2. peer rows of direction d's peers: pod peers in identity space, expanded over word runs
 // (skipped in IDO mode: the class rows expand them); IP peers per pod
@@ -54,7 +47,7 @@ static void enq_peer_rows(cyc_ctx* c, int d, hipStream_t st, int which = PEERS_P
   const uint32_t P = pb.P, W = pb.W;
   const uint32_t E = c->dir[1].n;
   // d = 2: both directions in one launch (their peer sub-lists are adjacent) when they share a window
-  if (d == 2 && !one_window(c)) {
+  if (d == 2 && !c->route.one_window) {
     enq_peer_rows(c, 0, st, which);
     enq_peer_rows(c, 1, st, which);
     return;
@@ -64,7 +57,7 @@ static void enq_peer_rows(cyc_ctx* c, int d, hipStream_t st, int which = PEERS_P
   peer_window(c, d == 2 ? 1 : d, w0, nw);
   peer_chunks(c, d == 2 ? 1 : d, c0, nch);
   const uint32_t r0 = c->rp_off[dlo], Rp = (which & PEERS_POD) ? c->rp_off[dhi] - r0 : 0u;
-  if (Rp && E && W && ido_mode(c)) {
+  if (Rp && E && W && c->route.ido) {
     const uint32_t EW = (E + 63) / 64;
     for (int x = dlo; x < dhi; x++) {  // per direction: its identity word window
       const uint32_t u0 = c->rpu_off[x], Ru = c->rpu_off[x + 1] - u0;  // distinct matchers only
@@ -76,7 +69,7 @@ static void enq_peer_rows(cyc_ctx* c, int d, hipStream_t st, int which = PEERS_P
             c->idob.as<uint64_t>() + uint64_t(u0) * EW, ew0, new_, c->ido_grp_ns.as<uint2>() + c->ido_goff[x],
             c->ido_word_ns.as<uint2>());
     }
-  } else if (Rp && E && nw && (c->pod_rows >= 0 ? c->pod_rows == 1 : uint64_t(E) * 2 >= P)) {
+  } else if (Rp && E && nw && c->route.pod_direct) {
     const uint32_t* plist = c->pod_peers.as<uint32_t>() + r0;
     const unsigned g = unsigned((pod_direct_waves(Rp, nw) + 3) / 4);
     const uint32_t* eid = c->dir[1].pod_id.as<uint32_t>();
@@ -149,10 +142,7 @@ static void enq_member(cyc_ctx* c, int d, hipStream_t st, bool clear = true) {
   if (clear && !class_rows_clear_ht(c, d)) enq_member_clear(c, d, st);
   MemberArgs ma = member_args(c, d);
   if (!c->n_act[d]) return;
-  // auto (-1): a wave per identity while identities are few (<= 4096) and each walks several
-  // targets (>= 4 on average): config #3 (2000 identities, ~6 targets each) gains, configs #2
-  // (10k identities), #4 (38k) and #5 (~0.3 targets each) lose (profiles/r01_member_wave_ab.txt)
-  if (c->member_wave > 0 || (c->member_wave < 0 && c->n_act[d] <= 4096 && c->act_targets[d] >= 4.0)) k_member_wave<<<unsigned((uint64_t(c->n_act[d]) + 3) / 4), 256, 0, st>>>(ma);
+  if (c->route.member_wave[d]) k_member_wave<<<unsigned((uint64_t(c->n_act[d]) + 3) / 4), 256, 0, st>>>(ma);
   else k_member<<<grid1(c->n_act[d], 128), 128, 0, st>>>(ma);
   k_classify<<<grid1(c->n_act[d], 256), 256, 0, st>>>(ma, dd.class_of.as<uint32_t>());
 }
@@ -166,11 +156,17 @@ static void enq_member(cyc_ctx* c, int d, hipStream_t st, bool clear = true) {
 
 // 6. class rows of direction d
 // IDO class rows: representatives per block (cyc_set_option "class_rpb"; 0 = auto: 4, or more in
-// the fused front, enq_front_fused), as many as fit the staged identity-set budget
+// the fused front, build_front), as many as fit the staged identity-set budget
 static uint32_t class_rpb(const cyc_ctx* c, size_t per_rep_lds, uint32_t want = 0) {
   const uint64_t fit = std::max<uint64_t>(1, IDO_LDS_BYTES / std::max<size_t>(per_rep_lds, 1));
   const int64_t w = want ? int64_t(want) : c->class_rpb_opt ? c->class_rpb_opt : 4;
   return uint32_t(std::max<int64_t>(1, std::min<int64_t>(w, int64_t(fit))));
+}
+// ... their LDS bytes per representative: set_rows identity sets (KC slot rows, or D descriptor rows)
+// + staged IP peers (+ alignment); and their blocks: (256-word group, KC slots, rpb representatives)
+static size_t ido_rep_lds(uint32_t set_rows, uint32_t EW) { return size_t(set_rows) * EW * 8 + IDO_IPL * sizeof(uint4) + 16; }
+static uint64_t ido_row_blocks(uint32_t WA, uint32_t K, uint32_t KC, uint32_t reps, uint32_t rpb) {
+  return uint64_t(ido_chunk_groups(WA)) * ((K + KC - 1) / KC) * ((reps + rpb - 1) / rpb);
 }
 
 static RowArgs row_args(cyc_ctx* c, int d) {
@@ -184,7 +180,7 @@ static RowArgs row_args(cyc_ctx* c, int d) {
   ra.ER = c->ER.as<uint64_t>();
   ra.portok = c->portok.as<uint8_t>();
   // descriptor bit rows of the port table (k_portbits; computed whenever D <= 32)
-  ra.portbits = port_bits_on(c) && pb.pms.size() && pb.descs.size() ? c->portbits.as<uint32_t>() : nullptr;
+  ra.portbits = c->route.port_bits && pb.pms.size() && pb.descs.size() ? c->portbits.as<uint32_t>() : nullptr;
   ra.D = D;
   ra.n_ident = dd.n;
   ra.K = K;
@@ -234,14 +230,6 @@ static RowArgs row_args(cyc_ctx* c, int d) {
   return ra;
 }
 
-// PM-build class rows a wave per 64-word chunk (pl_wave_chunks): both directions' accumulators fit
-// (descriptors and slots <= PL_NB) and every peer's port bits are available.
-static bool pl_wave_ok(const cyc_ctx* c) {
-  const Problem& pb = c->pb;
-  return c->pl_wave && pb.K <= PL_NB && pb.descs.size() <= PL_NB && pb.descs.size() && pb.pms.size() &&
-         port_bits_on(c) && pb.W <= 64 * 64;
-}
-
 static void enq_class_rows(cyc_ctx* c, int d, hipStream_t st) {
   Problem& pb = c->pb;
   const uint32_t K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
@@ -253,20 +241,19 @@ static void enq_class_rows(cyc_ctx* c, int d, hipStream_t st) {
     const unsigned g = unsigned(uint64_t((ra.WA + 255) / 256) * ((K + 7) / 8) * ra.rep_blocks);
     if (d == 0) k_class_rows<false><<<g, 256, 0, st>>>(ra);
     else k_class_rows<true><<<g, 256, 0, st>>>(ra);
-  } else if (ido_mode(c)) {
+  } else if (c->route.ido) {
     // identity sets first (one wave per representative and 4 slots / descriptors), then the rows
     const uint64_t waves = uint64_t(c->n_act[d]) * ((ra.NB + CI_G - 1) / CI_G);
     if (d == 0) k_class_ident<false, CI_G><<<unsigned((waves + 3) / 4), 256, 0, st>>>(ra);
     else k_class_ident<true, CI_G><<<unsigned((waves + 3) / 4), 256, 0, st>>>(ra);
     ra.ht_clear_words = 0;
-    const uint32_t rows = d == 0 ? 4u : D;  // (class_rows_ido_blk stages KC = 4 slot rows, or D descriptor rows)
-    const size_t per = size_t(rows) * ra.EW * 8 + IDO_IPL * sizeof(uint4) + 16;  // identity sets + staged IP peers (+ alignment)
+    const size_t per = ido_rep_lds(d == 0 ? 4u : D, ra.EW);  // (class_rows_ido_blk stages KC = 4 slot rows, or D descriptor rows)
     ra.rpb = class_rpb(c, per);
-    const unsigned gi = unsigned(uint64_t(ido_chunk_groups(ra.WA)) * ((K + 3) / 4) * ((c->n_act[d] + ra.rpb - 1) / ra.rpb));
+    const unsigned gi = unsigned(ido_row_blocks(ra.WA, K, 4, c->n_act[d], ra.rpb));
     if (d == 0) k_class_rows_ido<false, 4><<<gi, 256, per * ra.rpb, st>>>(ra);
     else k_class_rows_ido<true, 4><<<gi, 256, per * ra.rpb, st>>>(ra);
   } else {  // per-class flattened peer lists (the IP word spans are final here)
-    const bool wave = pl_wave_ok(c);
+    const bool wave = c->route.pl_wave;
     if (d == 0 && wave) k_class_rows_pl<false, true><<<pl_blocks(c, d), pl_threads(c), 0, st>>>(ra);
     else if (d == 0) k_class_rows_pl<false, false><<<pl_blocks(c, d), pl_threads(c), 0, st>>>(ra);
     else if (wave) k_class_rows_pl<true, true><<<pl_blocks(c, d), pl_threads(c), 0, st>>>(ra);
@@ -422,11 +409,7 @@ static bool enq_emit(cyc_ctx* c, hipStream_t st, uint64_t* out_in, uint64_t* out
   };
   if (rw[0] == rw[1] && nr[0] == nr[1]) {  // target rows: both planes in one launch
     ea.row_words = rw[0];
-    // alternate the planes' rows when each plane is >= 8 GB (config #3 on one GPU: emit 3.42 ->
-    // 3.11 ms on two of three boxes, -1 % on the third; 1-4 % slower for planes of <= 5 GB — 2, 4
-    // and 8 shards — profiles/r01_emit_interleave_sweep.txt)
-    ea.interleave = c->emit_interleave >= 0 ? uint32_t(c->emit_interleave)
-                                            : uint64_t(nr[0]) * rw[0] * 8 >= (8ull << 30) ? 1u : 0u;
+    ea.interleave = c->route.emit_interleave ? 1u : 0u;
     ea.n_rows[0] = ea.n_rows[1] = nr[0];
     if (part) {  // row phases (target rows over the whole table: both planes split at the same row)
       const uint32_t n1 = c->phase_n1[0];
@@ -462,51 +445,45 @@ static bool enq_emit(cyc_ctx* c, hipStream_t st, uint64_t* out_in, uint64_t* out
 
 // The fused front (k_front_a..e, one stream): the same block ranges the two-branch DAG launches
 // as ~15 kernels (enq_common, enq_peer_rows, enq_member, enq_class_rows), grouped by dependency
-// level.  Applies to no-panic builds with dense selectors whose pod-peer rows (PM builds) are
-// computed per pod in one level; returns false (nothing enqueued) otherwise.
-static bool front_fused_ok(const cyc_ctx* c) {
-  const Problem& pb = c->pb;
-  if (!c->front_fused || pb.may_err) return false;
-  if (!pb.P || !pb.K || !pb.W) return false;
-  if (uint64_t(c->n_sel) * pb.L && !c->dense_sel) return false;
-  if (ido_mode(c)) return true;
-  const uint32_t E = c->dir[1].n, Rp = c->rp_off[2] - c->rp_off[0];
-  return !(Rp && E) || (c->pod_rows >= 0 ? c->pod_rows == 1 : uint64_t(E) * 2 >= pb.P);
-}
+// level (Route::fused says where it applies).  build_front sizes it, launch_front issues it.
+struct FrontLaunches {
+  FrontA fa;
+  FrontB fb;
+  FrontC fc;
+  FrontRows fd, fe;
+  uint64_t ga = 0, gb = 0, gc = 0;     // blocks of launches A, B, C
+  uint32_t nd[3][2], ne[3][2];         // blocks of launches D and E per direction: [0] one pass, [1] / [2] a row phase's
+  size_t lds = 0, lds_uni = 0;         // launch E's LDS bytes (egress with one descriptor per slot: lds_uni)
+  uint32_t* span_fill = nullptr;       // the IP rows' word spans, set to ~0 by a memset before the launches
+  size_t span_fill_bytes = 0;          // (0: the previous run's emit reset them, or launch A does)
+  bool phases = false;
+  bool fits = true;                    // every launch's block count below 2^31 (else the DAG path runs)
+};
 
-// In-place class rows: the fused front with both output planes given.
-// Auto (-1): when the rows' identities are >= 1/16 of the rows (PM builds: config #4 emit -8 %,
-// #3u -7 %), and for identity-set (IDO) runs: config #3's class rows are 2 % of its rows,
-// and writing them into the planes saves their 400 MB of separate writes (3.286 -> 3.191 ms/step,
-// profiles/r05_inplace_sweep_ab.txt; over 5 plane placements in one process -2.1 / -0.0 / -0.1 /
-// -2.8 / -2.2 %, never slower: profiles/r05_plane_placement.txt; a source shard at N = 8 -1.2 %,
-// r05_shard_ab.txt; in round 2, before the current launch E, it lost 1 %).
-static bool inplace_ok(const cyc_ctx* c, const uint64_t* d_in, const uint64_t* d_eg) {
-  if (!c->class_inplace || !d_in || !d_eg || !front_fused_ok(c) || !c->pb.blocks.empty()) return false;
-  const uint64_t rows = uint64_t(std::max<int64_t>((c->rh[0] - c->rl[0] + c->rh[1] - c->rl[1]) / 2, 1));
-  return c->class_inplace == 1 || uint64_t(c->n_act[0] + c->n_act[1]) * 16 >= 2 * rows || ido_mode(c);
-}
-
+// Host arithmetic only: changes no context state and enqueues nothing.
 // out_in / out_eg non-null: the class rows go straight into those planes (in-place class rows; the
 // emit must then be enqueued with inplace = true).
-// mid (row phases, cyc_ctx::phase_split): enqueues phase 1's emit between the two class-row launches;
-// ev_mid0 / ev_mid1 (eager runs) bracket phase 2's class rows.
-static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nullptr, hipEvent_t ev_rows = nullptr,
-                            uint64_t* out_in = nullptr, uint64_t* out_eg = nullptr, const std::function<void()>* mid = nullptr,
-                            hipEvent_t ev_mid0 = nullptr, hipEvent_t ev_mid1 = nullptr) {
+// phases (row phases, Route::phase_split): the class rows as two launches, phase 1's emit between them.
+static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_in, uint64_t* out_eg, bool phases) {
   Problem& pb = c->pb;
   const uint32_t P = pb.P, K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
   const uint32_t M = uint32_t(pb.pms.size()), E = c->dir[1].n, EW = (E + 63) / 64;
-  bool fits = true;  // every launch's block count below 2^31 (else the DAG path runs)
+  FrontLaunches fl{};
+  fl.phases = phases;
+  bool& fits = fl.fits;
   auto blocks = [&fits](uint64_t n) {
     fits = fits && n < (1ull << 30);
     return uint32_t(n);
   };
+  FrontA& fa = fl.fa;
+  FrontB& fb = fl.fb;
+  FrontC& fc = fl.fc;
+  FrontRows &fd = fl.fd, &fe = fl.fe;
+  const bool ido = route.ido;
   // A: IP word spans | port table | slot words | selectors
-  FrontA fa{};
   fa.fill_p = c->ip_rng.as<uint32_t>();
   // the word spans and chunk masks of the IP rows and of PM builds' sparse pod rows (cnz needs no reset)
-  fa.fill_n = (c->Ri || c->Rr || (!ido_mode(c) && c->Rp)) ? pb.peers.size() * 4 : 0;
+  fa.fill_n = (c->Ri || c->Rr || (!ido && c->Rp)) ? pb.peers.size() * 4 : 0;
   fa.nb[0] = blocks((fa.fill_n + 255) / 256);
   fa.M = M;
   fa.D = D;
@@ -523,10 +500,7 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
   fa.VALID = c->VALID.as<uint64_t>();
   fa.DESCW = c->DESCW.as<int32_t>();
   fa.DM = c->DM.as<uint64_t>();
-  // the slot words (VALID / DESCW / DM per 64 destinations) serve only egress class rows whose
-  // destinations do not all share each slot's descriptor (uni_desc: the UNI class rows read udesc)
-  const bool slot_words = !c->uni_desc || !(ido_mode(c) || pl_wave_ok(c)) || !c->pb.blocks.empty();
-  fa.nb[2] = slot_words ? blocks((uint64_t(K) * W + 3) / 4) : 0u;
+  fa.nb[2] = route.slot_words ? blocks((uint64_t(K) * W + 3) / 4) : 0u;
   fa.S = c->n_sel;
   fa.L = pb.L;
   fa.sel_off = c->sel_off.as<uint32_t>();
@@ -535,12 +509,11 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
   fa.LVT = c->lvt.as<uint32_t>();
   fa.selres = c->selres.as<uint8_t>();
   fa.sel_list = c->sel_list.as<uint32_t>();
-  fa.nb[3] = uint64_t(c->n_sel) * pb.L && !lazy_sel(c) ? blocks(uint64_t(c->n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))) : 0u;
+  fa.nb[3] = uint64_t(c->n_sel) * pb.L && !route.lazy_sel ? blocks(uint64_t(c->n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))) : 0u;
   // B: IP rows | pod-peer identity sets (both directions' adjacent sub-lists) | membership x 2
   // Segments x = 0, 1 of the IP rows and per-pod pod rows: the directions' sub-lists with their own
   // word windows (source shards), or both directions in segment 0 (one window)
-  const bool one_win = one_window(c);
-  FrontB fb{};
+  const bool one_win = route.one_window;
   fb.P = P;
   fb.W = W;
   fb.ip_ex = c->ip_ex.as<DCidr>();
@@ -594,9 +567,7 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
     fb.new_[x] = x == 0 ? c->ido_ew1 - c->ido_ew0 : EW;
     fb.nb[2 + x] = (fb.Ru_[x] && E && fb.new_[x]) ? blocks((uint64_t((fb.Ru_[x] + PB_GROUP - 1) / PB_GROUP) * fb.new_[x] + 3) / 4) : 0u;
   }
-  const bool ido = ido_mode(c);
-  FrontC fc{};
-  if (!ido && !pod_sparse(c)) {  // PM builds, few pod-peer words: full rows, a wave per (pod peer, word)
+  if (!ido && !route.pod_sparse) {  // PM builds, few pod-peer words: full rows, a wave per (pod peer, word)
     fb.pod_direct = 1;
     fb.pod_eid = c->dir[1].pod_id.as<uint32_t>();
     for (int x = 0; x < 2; x++) {
@@ -640,22 +611,18 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
       fc.nb[4 + x] = E && fc.nch[x] && !(one_win && x) ? c->post_off[dhi] - c->post_off[dlo] : 0u;  // a block per posting-built peer
     }
   }
-  FrontRows fd{}, fe{};
-  size_t lds = 0, lds_uni = 0, e_per[2] = {0, 0};
-  uint32_t e_na[2] = {0, 0};
-  // row phases: the class rows in two launches with phase 1's emit between them (the caller's mid)
-  const bool phases = c->phase_split && mid;
-  c->phase_used = phases ? 2 : 0;
+  size_t &lds = fl.lds, &lds_uni = fl.lds_uni, e_per[2] = {0, 0};
+  uint32_t na_all[2];  // active identities per direction
   for (int d = 0; d < 2; d++) {
-    const uint32_t na = c->dir[d].n ? c->n_act[d] : 0u;
+    const uint32_t na = na_all[d] = c->dir[d].n ? c->n_act[d] : 0u;
     fb.ma[d] = member_args(c, d);
     fc.ma[d] = fb.ma[d];
     if (phases) {  // the class election lists phase 2's classes apart (from the tail of reps[])
       fc.ma[d].first_row = c->arow[d].as<uint32_t>();
-      fc.ma[d].split = c->phase_split;
+      fc.ma[d].split = route.phase_split;
     }
     fc.class_of[d] = c->dir[d].class_of.as<uint32_t>();
-    fb.member_wave[d] = c->member_wave > 0 || (c->member_wave < 0 && na <= 4096 && c->act_targets[d] >= 4.0);
+    fb.member_wave[d] = route.member_wave[d];
     fb.nb[4 + d] = na ? blocks(fb.member_wave[d] ? (uint64_t(na) + 3) / 4 : (uint64_t(na) + 255) / 256) : 0u;
     fc.nb[d] = na ? blocks((uint64_t(na) + 255) / 256) : 0u;
     if (!na) continue;
@@ -670,7 +637,7 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
     if (!ido) {  // PM builds: launch D (k_front_d_pm) is the class rows from flattened peer lists
       fd.nb[d] = pl_blocks(c, d);
       if (d == 1 && c->uni_desc && c->pb.blocks.empty()) fd.ra[d].udesc = c->udesc.as<int32_t>();
-      fd.ra[d].pod_sparse = pod_sparse(c);  // pod rows from pod_rows_sparse_blk (launch C)
+      fd.ra[d].pod_sparse = route.pod_sparse;  // pod rows from pod_rows_sparse_blk (launch C)
       continue;
     }
     fe.ra[d] = fd.ra[d];
@@ -678,9 +645,7 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
     fd.nb[d] = blocks((uint64_t(na) * ((fd.ra[d].NB + CI_G - 1) / CI_G) + 3) / 4);
     // egress with one descriptor per slot (udesc): only the block's slots' sets are staged
     if (d == 1 && c->uni_desc) fe.ra[d].udesc = c->udesc.as<int32_t>();
-    e_per[d] = size_t(d == 0 || fe.ra[d].udesc ? uint32_t(E_KC) : D) * fd.ra[d].EW * 8 +
-               IDO_IPL * sizeof(uint4) + 16;  // identity sets + staged IP peers (+ alignment)
-    e_na[d] = na;
+    e_per[d] = ido_rep_lds(d == 0 || fe.ra[d].udesc ? uint32_t(E_KC) : D, fd.ra[d].EW);
   }
   // launch E's representatives per block: the most of 16 / 8 that still leaves >= 3000 blocks
   // (about two rounds of the chip's resident blocks: one block's staging latency is paid once per
@@ -689,9 +654,7 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
   // phases each of the two launches computes about half of the classes, so half of its blocks count
   // (config #3 phased E per step, 8 per block against 16: 121.4 vs 141.8 us on one box, 122.8 vs 123.8
   // on another — profiles/r06_class_rpb_ab.txt)
-  auto e_blocks = [&](int d, uint32_t rpb) {
-    return uint64_t(ido_chunk_groups(fe.ra[d].WA)) * ((K + E_KC - 1) / E_KC) * ((e_na[d] + rpb - 1) / rpb);
-  };
+  auto e_blocks = [&](int d, uint32_t rpb) { return ido_row_blocks(fe.ra[d].WA, K, E_KC, na_all[d], rpb); };
   uint32_t e_want = uint32_t(c->class_rpb_opt);
   if (!e_want) {
     e_want = 4;
@@ -714,7 +677,7 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
   }
   // membership ahead of the rest of launch B unless the IP rows alone fill the chip (~2k resident blocks)
   fb.member_first = uint64_t(fb.nb[0]) + fb.nb[1] < 2048;
-  const bool bits = fa.nb[1] && port_bits_on(c);
+  const bool bits = fa.nb[1] && route.port_bits;
   const uint32_t nb_bits = bits ? blocks((uint64_t(M) + 255) / 256) : 0u;
   fb.M = M;
   fb.D = D;
@@ -732,39 +695,55 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
     fb.bits_direct = 1;
     fb.nb[7] = fa.nb[1];
     fb.nb[8] = fa.nb[2];
-    if (fa.fill_n && !c->ip_rng_clean) HIPCHK(hipMemsetAsync(fa.fill_p, 0xFF, fa.fill_n * 4, st));
+    if (fa.fill_n && !c->ip_rng_clean) fl.span_fill = fa.fill_p, fl.span_fill_bytes = fa.fill_n * 4;
     fa.nb[0] = fa.nb[1] = fa.nb[2] = 0;
   }
-  const uint64_t ga = uint64_t(fa.nb[0]) + fa.nb[1] + fa.nb[2] + fa.nb[3];
-  uint64_t gb = 0, gc = 0;
-  for (uint32_t x : fb.nb) gb += x;
-  for (uint32_t x : fc.nb) gc += x;
-  if (!fits || gb >= (1ull << 31) || gc >= (1ull << 31)) return false;
-  if (ga) k_front_a<<<unsigned(ga), 256, 0, st>>>(fa);
-  if (gb) k_front_b<<<unsigned(gb), 256, 0, st>>>(fb);
-  if (gc) k_front_c<<<unsigned(gc), 256, 0, st>>>(fc);
-  if (ev_front) HIPCHK(hipEventRecord(ev_front, st));  // eager runs: phase timings
-  // the class rows: once, or per row phase with phase 1's emit between (the caller's mid)
-  // a phased launch's grid covers only the identities that can represent its phase's classes (the
-  // representatives' first rows decide the phase), not every active identity
-  const uint32_t fd_all[2] = {fd.nb[0], fd.nb[1]}, fe_all[2] = {fe.nb[0], fe.nb[1]};
+  fl.ga = uint64_t(fa.nb[0]) + fa.nb[1] + fa.nb[2] + fa.nb[3];
+  for (uint32_t x : fb.nb) fl.gb += x;
+  for (uint32_t x : fc.nb) fl.gc += x;
+  // the class rows' grids: one pass, or per row phase only the identities that can represent the
+  // phase's classes (the representatives' first rows decide the phase), not every active identity
+  for (uint32_t phase = 0; phase < 3; phase++)
+    for (int d = 0; d < 2; d++) {
+      fl.nd[phase][d] = fd.nb[d];
+      fl.ne[phase][d] = fe.nb[d];
+      if (!CYC_PHASE_GRID || !phase) continue;
+      const uint32_t nph = phase == 1 ? c->n_act_ph1[d] : na_all[d] - c->n_act_ph1[d];
+      if (ido && fe.nb[d]) fl.ne[phase][d] = blocks(ido_row_blocks(fe.ra[d].WA, K, E_KC, nph, fe.ra[d].rpb));
+      else if (!ido && fd.nb[d]) fl.nd[phase][d] = std::min(fd.nb[d], nph);
+    }
+  fits = fits && fl.gb < (1ull << 31) && fl.gc < (1ull << 31);
+  return fl;
+}
+
+// The events an eager run records for its phase timings (graph / eager-DAG runs: none)
+struct FrontEvents {
+  hipEvent_t front = nullptr, rows = nullptr;  // after launches A-C; after the (first phase's) class rows
+  hipEvent_t mid0 = nullptr, mid1 = nullptr;   // around phase 2's class rows
+};
+
+// Issues what build_front sized.  mid (row phases): enqueues phase 1's emit between the two class-row launches.
+template <class Mid>
+static void launch_front(cyc_ctx* c, hipStream_t st, FrontLaunches& fl, const FrontEvents& ev, const Mid& mid) {
+  FrontRows &fd = fl.fd, &fe = fl.fe;
+  const bool ido = c->route.ido;
+  if (fl.span_fill) HIPCHK(hipMemsetAsync(fl.span_fill, 0xFF, fl.span_fill_bytes, st));
+  if (fl.ga) k_front_a<<<unsigned(fl.ga), 256, 0, st>>>(fl.fa);
+  if (fl.gb) k_front_b<<<unsigned(fl.gb), 256, 0, st>>>(fl.fb);
+  if (fl.gc) k_front_c<<<unsigned(fl.gc), 256, 0, st>>>(fl.fc);
+  if (ev.front) HIPCHK(hipEventRecord(ev.front, st));  // eager runs: phase timings
+  if (ido && fd.nb[0] + fd.nb[1]) k_front_d<<<fd.nb[0] + fd.nb[1], 256, 0, st>>>(fd);  // identity sets: once
+  // the class rows: once, or per row phase with phase 1's emit between (mid)
   auto class_rows = [&](uint32_t phase) {
     for (int d = 0; d < 2; d++) {
-      RowArgs& ra = ido ? fe.ra[d] : fd.ra[d];
-      ra.phase = phase;
-      if (!CYC_PHASE_GRID || !phase) continue;
-      const uint32_t na = c->dir[d].n ? c->n_act[d] : 0u;
-      const uint32_t nph = phase == 1 ? c->n_act_ph1[d] : na - c->n_act_ph1[d];
-      if (ido) {
-        if (fe_all[d]) fe.nb[d] = blocks(uint64_t(ido_chunk_groups(fe.ra[d].WA)) * ((K + E_KC - 1) / E_KC) *
-                                         ((nph + fe.ra[d].rpb - 1) / fe.ra[d].rpb));
-      } else if (fd_all[d]) {
-        fd.nb[d] = std::min(fd_all[d], nph);
-      }
+      (ido ? fe : fd).ra[d].phase = phase;
+      fd.nb[d] = fl.nd[phase][d];
+      fe.nb[d] = fl.ne[phase][d];
     }
+    const size_t lds = fl.lds, lds_uni = fl.lds_uni;
     if (!ido) {
       const unsigned gd = fd.nb[0] + fd.nb[1];
-      if (gd && pl_wave_ok(c)) k_front_d_pm<true><<<gd, pl_threads(c), 0, st>>>(fd);
+      if (gd && c->route.pl_wave) k_front_d_pm<true><<<gd, pl_threads(c), 0, st>>>(fd);
       else if (gd) k_front_d_pm<false><<<gd, pl_threads(c), 0, st>>>(fd);
     } else if (fe.nb[0] && fe.nb[1] && fe.ra[1].udesc) {
       k_front_e_uni<<<fe.nb[0] + fe.nb[1], 256, std::max(lds, lds_uni), st>>>(fe);
@@ -775,15 +754,32 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
       if (fe.nb[0]) k_class_rows_ido<false, E_KC><<<fe.nb[0], 256, lds, st>>>(fe.ra[0]);
     }
   };
-  if (ido && fd.nb[0] + fd.nb[1]) k_front_d<<<fd.nb[0] + fd.nb[1], 256, 0, st>>>(fd);  // identity sets: once
-  class_rows(phases ? 1u : 0u);
-  if (ev_rows) HIPCHK(hipEventRecord(ev_rows, st));
-  if (phases) {
-    (*mid)();
-    if (ev_mid0) HIPCHK(hipEventRecord(ev_mid0, st));
+  class_rows(fl.phases ? 1u : 0u);
+  if (ev.rows) HIPCHK(hipEventRecord(ev.rows, st));
+  if (fl.phases) {
+    mid();
+    if (ev.mid0) HIPCHK(hipEventRecord(ev.mid0, st));
     class_rows(2u);
-    if (ev_mid1) HIPCHK(hipEventRecord(ev_mid1, st));
+    if (ev.mid1) HIPCHK(hipEventRecord(ev.mid1, st));
   }
+}
+
+// The skeleton enqueue_pipeline and capture_pipeline share: the in-place decision, the fused front and its
+// emit (row phases: part 1 between the class-row launches, then part 2).  Returns false with nothing
+// enqueued and phase_used == 0 when the front is not fused (the caller's fallback runs); else
+// *status_done = the emit wrote the status plane.
+static bool enq_fused_step(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status, const FrontEvents& ev,
+                           bool* status_done) {
+  const Route& route = c->route;
+  c->phase_used = 0;
+  if (!route.fused) return false;
+  const bool ip = route.inplace && d_in && d_eg;
+  const bool phases = route.phase_split != 0;
+  FrontLaunches fl = build_front(c, route, ip ? d_in : nullptr, ip ? d_eg : nullptr, phases);
+  if (!fl.fits) return false;
+  if (phases) c->phase_used = 2;
+  launch_front(c, st, fl, ev, [&] { enq_emit(c, st, d_in, d_eg, d_status, ip, 1); });
+  *status_done = enq_emit(c, st, d_in, d_eg, d_status, ip, phases ? 2 : 0);
   return true;
 }
 
@@ -792,20 +788,16 @@ static bool enq_front_fused(cyc_ctx* c, hipStream_t st, hipEvent_t ev_front = nu
 static void enqueue_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status) {
   Problem& pb = c->pb;
   HIPCHK(hipEventRecord(c->ev[0], st));
-  const bool ip = inplace_ok(c, d_in, d_eg);
-  c->phase_used = 0;
-  const std::function<void()> mid = [&] { enq_emit(c, st, d_in, d_eg, d_status, ip, 1); };
-  const bool fused = front_fused_ok(c) && enq_front_fused(c, st, c->ev[1], c->ev[2], ip ? d_in : nullptr, ip ? d_eg : nullptr,
-                                                          &mid, c->ev_p[0], c->ev_p[1]);
-  if (!fused) {
+  bool status_done = false;
+  if (!enq_fused_step(c, st, d_in, d_eg, d_status, FrontEvents{c->ev[1], c->ev[2], c->ev_p[0], c->ev_p[1]}, &status_done)) {
     enq_common(c, st);
     for (int d = 0; d < 2; d++) enq_peer_rows(c, d, st);
     for (int d = 0; d < 2; d++) enq_member(c, d, st);
     HIPCHK(hipEventRecord(c->ev[1], st));
     for (int d = 0; d < 2; d++) enq_class_rows(c, d, st);
     HIPCHK(hipEventRecord(c->ev[2], st));
+    status_done = enq_emit(c, st, d_in, d_eg, d_status);
   }
-  const bool status_done = enq_emit(c, st, d_in, d_eg, d_status, ip && fused, c->phase_used ? 2 : 0);
   HIPCHK(hipEventRecord(c->ev[3], st));
   if (!status_done && d_status && uint64_t(pb.P) * pb.K)
     HIPCHK(hipMemcpyAsync(d_status, c->slot_status.p, uint64_t(pb.P) * pb.K, hipMemcpyDeviceToDevice, st));
@@ -818,11 +810,9 @@ static void enqueue_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_
 static void capture_pipeline(cyc_ctx* c, hipStream_t st, hipStream_t st2, hipStream_t st3, uint64_t* d_in, uint64_t* d_eg,
                              uint8_t* d_status) {
   Problem& pb = c->pb;
-  const bool ip = inplace_ok(c, d_in, d_eg);
-  c->phase_used = 0;
-  const std::function<void()> mid = [&] { enq_emit(c, st, d_in, d_eg, d_status, ip, 1); };
-  if (front_fused_ok(c) && enq_front_fused(c, st, nullptr, nullptr, ip ? d_in : nullptr, ip ? d_eg : nullptr, &mid)) {
-    if (enq_emit(c, st, d_in, d_eg, d_status, ip, c->phase_used ? 2 : 0)) return;
+  bool status_done = false;
+  if (enq_fused_step(c, st, d_in, d_eg, d_status, FrontEvents{}, &status_done)) {
+    if (status_done) return;
   } else {
     HIPCHK(hipEventRecord(c->fork_ev, st));
     HIPCHK(hipStreamWaitEvent(st3, c->fork_ev, 0));
@@ -958,13 +948,17 @@ static int run_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_
     return fail(c, CYC_ERR_ARG, "source rows: row_lo must be a multiple of 64, row_hi too unless it is the pod count");
   if (c->order_lo != lo || c->order_hi != hi || c->order_src != src) drop_graph(c);  // range plan buffers are re-made
   ensure_range(c, lo, hi, src);
-  if (!c->plvt_ready && front_fused_ok(c) && pod_sparse(c)) {
+  const Route& route = c->route;
+  if (!c->plvt_ready && route.fused && route.pod_sparse) {
     drop_graph(c);  // a graph captured without the per-pod table would keep the slower gathers
     ensure_plvt(c, st);
   }
-  int graphs = c->use_graphs >= 0 ? c->use_graphs : (front_fused_ok(c) ? 2 : 1);
-  if (graphs == 1 && !allow_capture) graphs = 2;
-  if (graphs == 2 && !pb.may_err) {
+  const bool dag = route.launch == 2 || !allow_capture;  // (of the runs that are not eager)
+  if (route.runs_eager) {
+    enqueue_pipeline(c, st, d_in, d_eg, d_status);
+    c->timed = true;
+    c->timed_graph = false;
+  } else if (dag) {
     // the graph's DAG, enqueued directly: the caller's stream forks to two internal streams and
     // joins them back before the emit (events), without hipGraphLaunch's per-replay latency
     ensure_cap_streams(c);
@@ -973,7 +967,7 @@ static int run_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_
     if (c->step_events) HIPCHK(hipEventRecord(c->ev[3], st));
     c->timed = c->step_events != 0;
     c->timed_graph = true;
-  } else if (graphs && !pb.may_err) {
+  } else {
     // The whole pipeline as one hipGraph (captured once per output buffers / row range):
     // removes the host launch cost of ~16 launches per run (dominant on small problems).
     const void* key[6] = {d_in, d_eg, d_status, reinterpret_cast<void*>(lo), reinterpret_cast<void*>(hi),
@@ -1003,10 +997,6 @@ static int run_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_
     if (c->step_events) HIPCHK(hipEventRecord(c->ev[3], st));
     c->timed = c->step_events != 0;
     c->timed_graph = true;
-  } else {
-    enqueue_pipeline(c, st, d_in, d_eg, d_status);
-    c->timed = true;
-    c->timed_graph = false;
   }
   c->ran = true;
   c->last_stream = st;  // cyc_last_classes waits for this stream only

@@ -122,10 +122,26 @@ static uint64_t ido_lds_bytes(const cyc_ctx* c) {  // k_class_rows_ido: staged i
   return std::max<uint64_t>(std::min<uint64_t>(8, c->pb.K), D) * EW * 8;  // KC <= 8 slot rows or D
 }
 
-static bool ido_possible(const cyc_ctx* c) {
-  return !c->pb.may_err && c->plan.max_runs <= IDO_MAX_RUNS && ido_lds_bytes(c) <= IDO_LDS_BYTES &&
-         ido_b_bytes(c, 0) + ido_b_bytes(c, 1) <= (1ull << 30);
+// The route's facts as the context holds them now: options, the prepared problem, the current range plan.
+static RouteIn route_in(const cyc_ctx* c) {
+  const Problem& pb = c->pb;
+  RouteIn in;
+  in.use_graphs = c->use_graphs, in.front_fused = c->front_fused, in.pod_words = c->pod_words, in.pod_rows = c->pod_rows;
+  in.member_wave = c->member_wave, in.pl_wave = c->pl_wave, in.sel_lazy = c->sel_lazy, in.pr_group = c->pr_group;
+  in.class_inplace = c->class_inplace, in.emit_interleave = c->emit_interleave, in.row_phases = c->row_phases;
+  in.P = pb.P, in.K = pb.K, in.W = pb.W, in.L = pb.L;
+  in.n_desc = uint32_t(pb.descs.size()), in.n_pm = uint32_t(pb.pms.size());
+  in.may_err = pb.may_err, in.blocks = !pb.blocks.empty();
+  in.dense_sel = c->dense_sel, in.uni_desc = c->uni_desc, in.n_sel = c->n_sel, in.max_runs = c->plan.max_runs;
+  in.ido_lds_bytes = ido_lds_bytes(c), in.ido_b_bytes = ido_b_bytes(c, 0) + ido_b_bytes(c, 1);
+  in.E = c->dir[1].n;
+  for (int d = 0; d < 2; d++) in.n_act[d] = c->n_act[d], in.act_targets[d] = c->act_targets[d], in.rows[d] = c->rh[d] - c->rl[d];
+  std::copy(c->rp_off, c->rp_off + 3, in.rp_off);
+  in.win_w0 = c->win_w0, in.win_wa = c->win_wa;
+  in.whole = c->rl[1] == 0 && c->rh[1] == int64_t(pb.P), in.src = c->order_src;
+  return in;
 }
+static void reroute(cyc_ctx* c) { c->route = resolve_route(route_in(c)); }
 
 // Batched blocks: per block (first pod, pods, first slot, slots) and its output slab offsets; per
 // identity its block and class-row window (its block's words).
@@ -462,7 +478,7 @@ static void prepare_device(cyc_ctx* c) {
     dd.A.alloc(std::max<uint64_t>(uint64_t(dd.n) * K * W * 8, 16));
     if (pb.may_err) dd.AE.alloc(std::max<uint64_t>(uint64_t(dd.n) * K * W * 8, 16));
     else dd.AE.alloc(0);
-    dd.B.alloc(ido_possible(c) ? std::max<uint64_t>(ido_b_bytes(c, d), 16) : 16);
+    dd.B.alloc(ido_possible(route_in(c)) ? std::max<uint64_t>(ido_b_bytes(c, d), 16) : 16);
     {  // IP-peer list bounds per identity: the IP peers of its namespace's targets
       // (upper bound for both list uses: IDO builds list the IP peers, PM builds every peer)
       std::vector<uint32_t> ns_ip(pb.strings.size(), 0), off(dd.n + 1, 0);
@@ -477,6 +493,7 @@ static void prepare_device(cyc_ctx* c) {
   prepare_blocks_device(c);
   c->order_lo = c->order_hi = -1;
   c->order_src = false;
+  reroute(c);
 }
 
 // nonzero-chunk flags of the IP peers' PM rows, after the word spans and chunk masks in the ip_rng buffer
@@ -484,26 +501,12 @@ static uint32_t* ip_cnz(cyc_ctx* c) { return c->ip_rng.as<uint32_t>() + 4 * c->p
 
 static unsigned grid1(uint64_t n, unsigned block) { return unsigned(std::min<uint64_t>((n + block - 1) / block, 1u << 20)); }
 
-static bool front_fused_ok(const cyc_ctx* c);
-static bool ido_mode(const cyc_ctx* c);
-// Selectors evaluated where used (sel_at through LVT), not as the dense SELRES table: the fused
-// front of PM builds (its pod-peer rows and membership are the only selector users, and PM builds
-// are the ones whose label sets number ~ the pods).  The DAG path computes SELRES regardless.
-// PM builds' fused front: sparse pod-peer rows (pod_rows_sparse_blk, launch C) once the rows are
-// large (>= 2M pod-peer words: config #3u), else full rows a wave per (pod peer, word) in launch B,
-// which has the parallelism small problems need (config #2: 125k peer words, B + C 33 vs 52 us).
-// pr_group > 0 forces the sparse rows.
-static bool pod_sparse(const cyc_ctx* c) {
-  if (ido_mode(c)) return false;
-  const uint64_t Rp = c->rp_off[2] - c->rp_off[0];
-  return c->pr_group > 0 || Rp * c->pb.W >= (2ull << 20);
-}
 // PLVT (each pod's value of every dense label key) for the sparse pod-peer rows: gathered on the
 // device from LVT once per prepare, on the run's stream ahead of the step, when a run needs it
 // and it fits PLVT_MAX_BYTES; otherwise the rows read LVT through each pod's label set (SelView
 // with PLVT null), one more dependent load per pod.
 static void ensure_plvt(cyc_ctx* c, hipStream_t st) {
-  if (c->plvt_ready || !c->dense_sel || !pod_sparse(c)) return;
+  if (c->plvt_ready || !c->dense_sel || !c->route.pod_sparse) return;
   const uint64_t n = uint64_t(c->n_lkeys + 1) * c->pb.P;
   if (!n || n * 4 > (uint64_t(c->plvt_max_mb) << 20)) return;
   c->plvt.alloc(n * 4);
@@ -512,21 +515,9 @@ static void ensure_plvt(cyc_ctx* c, hipStream_t st) {
   HIPCHK(hipGetLastError());
   c->plvt_ready = true;
 }
-static bool lazy_sel(const cyc_ctx* c) {
-  if (!c->dense_sel || c->pb.may_err || c->sel_lazy == 0 || !front_fused_ok(c)) return false;
-  const bool pod_peers = c->rp_off[2] > c->rp_off[0];
-  // no pod-peer rows at all (IPBlock-only policies, config #4): the membership is the only selector
-  // user, one record and one label-table load per target — no table, and no launch A
-  if (!pod_peers && c->sel_lazy < 0) return true;
-  // auto: lazy once the dense table would take ~0.1 ms (>= 64M pairs; config #3u: 0.75G pairs,
-  // 1.1 ms; config #2 stays dense — its multi-requirement selectors cost more evaluated per use)
-  // IDO builds always: their identity sets and membership evaluate fewer pairs than the table
-  // holds (config #3: A + B 118 -> 111 us; its N = 8 shard 35 -> 31 us, profiles/r02_sel_lazy_ab.txt)
-  return c->sel_lazy == 1 || ido_mode(c) || uint64_t(c->n_sel) * c->pb.L >= (64ull << 20);
-}
 static SelView sel_view(cyc_ctx* c) {
   SelView v{};
-  v.selres = lazy_sel(c) ? nullptr : c->selres.as<uint8_t>();
+  v.selres = c->route.lazy_sel ? nullptr : c->selres.as<uint8_t>();
   v.L = c->pb.L;
   v.sel_off = c->sel_off.as<uint32_t>();
   v.req_vals = c->req_vals.as<uint32_t>();
@@ -585,8 +576,18 @@ static uint32_t pl_blocks(const cyc_ctx* c, int d) { return std::min<uint32_t>(c
 // k): egress rows of sources [lo, hi) (full rows) and the ingress rows of EVERY destination, but
 // only their words [lo / 64, ceil(hi / 64)) — the shard's sources as peers.  lo must be a multiple
 // of 64 and hi too unless it is P (checked by the caller), so the windows of a partition tile the words.
-static void peer_chunks(const cyc_ctx* c, int d, uint32_t& c0, uint32_t& nch);
-static bool one_window(const cyc_ctx* c);
+// Word window of direction d's peer rows in the current plan: [w0, w0 + nw); as 64-word chunks
+// [c0, c0 + nch).
+static void peer_window(const cyc_ctx* c, int d, uint32_t& w0, uint32_t& nw) {
+  w0 = d == 0 ? c->win_w0 : 0u;
+  nw = d == 0 ? c->win_wa : c->pb.W;
+}
+static void peer_chunks(const cyc_ctx* c, int d, uint32_t& c0, uint32_t& nch) {
+  uint32_t w0, nw;
+  peer_window(c, d, w0, nw);
+  c0 = w0 / 64;
+  nch = nw ? (w0 + nw + 63) / 64 - c0 : 0u;
+}
 // Host restatement of ip_rows_fast_blk's chunk test: false when network n misses the chunk's pods'
 // addresses of its family (or the chunk has none of that family).
 static bool ip_chunk_touch(const DCidr& n, const DWordIP& ck) {
@@ -608,6 +609,8 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
   if (c->order_lo == lo && c->order_hi == hi && c->order_src == src) return;
   Problem& pb = c->pb;
   PhaseClock clk("range plan");
+  c->order_lo = c->order_hi = -1;  // (no plan until this one is complete)
+  c->order_src = src;
   c->rl[0] = src ? 0 : lo;
   c->rh[0] = src ? int64_t(pb.P) : hi;
   c->rl[1] = lo;
@@ -630,18 +633,15 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
       c->ido_ew1 = e0 == UINT32_MAX ? 0u : (e1 + 63) / 64;
     }
   }
-  // row phases (cyc_ctx::row_phases): a whole no-panic table splits at row P/2 — auto once each plane
-  // is >= 8 GB; the emit lists then hold the rows before the split first
-  const bool whole = lo == 0 && hi == int64_t(pb.P) && (!src || c->win_wa == pb.W);
-  const bool big = uint64_t(pb.P) * pb.K * pb.W * 8 >= (8ull << 30);
-  c->phase_split = c->row_phases != 1 && whole && !pb.may_err && pb.blocks.empty() && pb.P >= 128 &&
-                           (c->row_phases == 2 || big) ? uint32_t(pb.P / 2) : 0u;
+  // the answers that rest on the rows and window alone: the plan below is built by them (row phases:
+  // the emit lists hold the rows before the split first)
+  const Route by_window = resolve_route(route_in(c));
+  const uint32_t split = by_window.phase_split;
   for (int d = 0; d < 2; d++) {  // emit row order: clustered by this direction's identity, (pod, identity) pairs
     std::vector<uint32_t> ord(size_t(c->rh[d] - c->rl[d]));
     std::iota(ord.begin(), ord.end(), uint32_t(c->rl[d]));
     const auto& i1 = c->ids[d].of_pod;
     const auto& i2 = c->ids[1 - d].of_pod;
-    const uint32_t split = c->phase_split;
     std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
       if (split && (x < split) != (y < split)) return x < split;
       return i1[x] != i1[y] ? i1[x] < i1[y] : i2[x] < i2[y];
@@ -676,7 +676,7 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
       upload(c->arow[d], ar);
       c->n_act_ph1[d] = 0;  // (row phases: the phase-1 launch's representatives are among these)
       for (uint32_t i : act)
-        if (c->phase_split && ar[i] < c->phase_split) c->n_act_ph1[d]++;
+        if (split && ar[i] < split) c->n_act_ph1[d]++;
     }
     std::vector<uint8_t> ns_needed(pb.strings.size(), 0);
     for (uint32_t i : act) ns_needed[I.ns[i]] = 1;
@@ -959,7 +959,7 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
      // ip_rows_fast_blk), IPI_TOUCH to a wave, and the others 64 to a wave (their chunk flags cleared)
     std::vector<DIPItem> items;
     std::vector<uint32_t> il;
-    const bool one = one_window(c);
+    const bool one = by_window.one_window;
     const uint32_t NCH = (pb.W + 63) / 64;
     // auto: whole-table runs only — a shard's few IP rows and windows ran launch B 2x slower as items
     // (config #3 rank 0 of 8: B 45.5 vs 20.9 us source, 36.4 vs 17.0 target; whole step +20 us), while
@@ -998,20 +998,5 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
   clk.lap("done");
   c->order_lo = lo;
   c->order_hi = hi;
-  c->order_src = src;
+  reroute(c);  // (the plan's facts are complete: the route of this prepare, option set, row range and partition)
 }
-
-// Word window of direction d's peer rows in the current plan: [w0, w0 + nw); as 64-word chunks
-// [c0, c0 + nch).
-static void peer_window(const cyc_ctx* c, int d, uint32_t& w0, uint32_t& nw) {
-  w0 = d == 0 ? c->win_w0 : 0u;
-  nw = d == 0 ? c->win_wa : c->pb.W;
-}
-static void peer_chunks(const cyc_ctx* c, int d, uint32_t& c0, uint32_t& nch) {
-  uint32_t w0, nw;
-  peer_window(c, d, w0, nw);
-  c0 = w0 / 64;
-  nch = nw ? (w0 + nw + 63) / 64 - c0 : 0u;
-}
-// the two directions' peer rows share one window (target-row plans): one launch segment for both
-static bool one_window(const cyc_ctx* c) { return c->win_w0 == 0 && c->win_wa == c->pb.W; }

@@ -897,7 +897,7 @@ def test_launch_modes_and_knobs(gpu):
                     ("nope", 0)):
         with pytest.raises(Exception):
             eng.set_option(name, v)
-    # a build that may panic keeps the graph path (the panic walk needs the ordered peer rows)
+    # a build that may panic keeps the unfused pipeline, run eagerly (the panic walk needs the ordered peer rows)
     pols_b, res_b, probes_b = random_problem(81_003, n_pods=60, bad=True)
     eng_b = Engine(0).build_policies(pols_b).load_resources(res_b)
     try:
