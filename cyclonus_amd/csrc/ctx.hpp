@@ -50,9 +50,21 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
-struct DevBuf {
+struct DevBuf {  // owns a hipMalloc: movable, not copyable
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      if (p) (void)hipFree(p);
+      p = o.p, bytes = o.bytes;
+      o.p = nullptr, o.bytes = 0;
+    }
+    return *this;
+  }
   ~DevBuf() {
     if (p) (void)hipFree(p);
   }
@@ -103,114 +115,109 @@ struct PeerPlan {
   uint32_t max_runs = 0;  // most identity runs in one 64-pod word
   std::vector<WordRuns> runs;  // [W] when max_runs <= IDO_MAX_RUNS
 };
-struct cyc_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  bool have_policy = false, have_res = false, prepared = false;
-  PolicyIR policy;
-  Resources res;
-  Problem pb;
+// The context's state, grouped by the one function that writes each group.
+
+// What a prepare makes (build_identities, prepare_device, prepare_blocks_device, and ensure_plvt on the
+// first run that needs the per-pod label table).  A prepare starts from Prepared{}.
+struct Prepared {
   Identities ids[2];
   // device tables
   DevBuf ls_off, ls_key, ls_val, sel_off, reqs, req_vals, pod_ns, pod_ls, pod_nsls, pod_ip, cidrs, ipbs, ipb_ex, pms,
       pents, peers, descs, slot_desc, slot_status, slot_cfg, slot_idx;
-  DevBuf selres, PM, ER, portok, portbits, VALID, DESCW, DM, first_err, order[2];
+  DevBuf selres, PM, ER, portok, portbits, VALID, DESCW, DM, first_err;
   DevBuf status_sink;  // status plane target of graph runs given no status pointer (see capture_pipeline)
-  // peer-row stage: pod peers in identity space + per-word identity runs; IP peers per pod
-  DevBuf pod_peers_u;  // identity-set (IDOB) rows: the needed pod peers, one per distinct
-                       // (namespace matcher, pod selector) of a direction (peer_ido maps every peer)
-  DevBuf pod_peers, ip_peers, ip_tests, ip_ex, id_nsls, word_off, run_e, run_mask, ido, ip_words, peer_ido, peer_row, zeros, idob, runs, ip_rng, lvt, dreqs;
-  std::vector<uint32_t> prow_host;  // peer_row on the host (the panic describer reads PM / ER rows by it)
+  // peer-row stage: per-word identity runs, pod-peer outcomes in identity space
+  DevBuf id_nsls, word_off, run_e, run_mask, runs, ido, idob, ip_words, zeros, lvt, dreqs;
+  DevBuf ip_rng;  // per peer: its IP row's word span and chunk masks, then its nonzero-chunk flags (ip_cnz)
+  // ip_rng's span records are all ~0: the last enqueued run's emit reset them (EmitArgs::reset), so the
+  // next fused front needs no fill before its IP rows (and, without a selector table, no launch A)
+  bool ip_rng_clean = false;
   DevBuf udesc;     // per slot the one VALID descriptor every pod has, when all slots are so (uni_desc)
   bool uni_desc = false;
-  DevBuf plvt;      // LVT per pod (SelView::PLVT), built by ensure_plvt when it fits PLVT_MAX_BYTES
+  DevBuf plvt;      // LVT per pod (SelView::PLVT), built by ensure_plvt when it fits "plvt_max_mb"
   uint32_t n_lkeys = 0;     // dense label keys (LVT rows - 1)
   bool plvt_ready = false;
-  int64_t plvt_max_mb = 1024;  // "plvt_max_mb": largest PLVT built (0: never, the LVT gathers instead)
   DevBuf sel_one;   // SelView::one
-  std::vector<uint4> sel_one_h;  // its host copy (the identity-set peer records, pb_rec)
-  // per identity-set row (pod_peers_u): its matcher as three 16-byte records — (namespace matcher kind,
-  // namespace / selector, pod selector, 0), then the namespace selector's and the pod selector's
-  // one-requirement records (SelView::one; SEL_ALL when there is none): peer_bits_blk loads a row
-  // group's records in one vector load instead of pod_peers -> peers -> one chains
-  DevBuf pb_rec;
+  std::vector<uint4> sel_one_h;  // its host copy (the identity-set peer records, RangePlan::pb_rec)
   DevBuf req_post, post_pods;  // label postings: per requirement (offset, count) x 2 values; pod lists
   std::vector<uint8_t> req_post_ok;  // the requirement's pods are its postings (EQ, IN of <= 2 values)
-  DevBuf pp_scan, pp_post;     // sparse pod rows: pod peers scanned per word / built from postings
-  uint32_t n_scan = 0, n_post = 0;
   DevBuf ns_words;  // DWordNS per 64-pod word, then per 64-word chunk (sparse pod rows)
   bool dense_sel = false;  // k_selectors_dense (LVT fits)
-  uint32_t Rp = 0, Ri = 0;
-  uint32_t rp_off[3] = {0, 0, 0}, ri_off[3] = {0, 0, 0};  // per-direction sub-lists (ingress, egress)
-  // IP rows built from address ranges (ip_rows_range_blk): the pods of each family sorted by
-  // address (host keys for the binary searches; the pod order on the device), and per direction the
-  // range-built rows
+  // The address index of the IP rows built from address ranges (ip_rows_range_blk): the pods of each
+  // family sorted by address (host keys for the binary searches; the pod order on the device)
   std::vector<uint32_t> ip4_key, ipsort_host;
-  std::vector<uint8_t> word_aff;  // per 64-pod word: bit f set when family f's pods there are affine (or absent)
   std::vector<std::array<uint32_t, 4>> ip6_key;
-  DevBuf ipsort, ipr_tests, ipr_iv;
-  uint32_t rr_off[3] = {0, 0, 0}, Rr = 0;
-  // IP rows as pod intervals (ip_rows_iv_blk): when a family's pods hold non-decreasing addresses in
-  // pod order (ip_mono[0] IPv4, [1] IPv6), a network less its excepts matches that family's pods in
-  // a few pod-index intervals; per direction the rows built that way
+  DevBuf ipsort;
+  std::vector<uint8_t> word_aff;  // per 64-pod word: bit f set when family f's pods there are affine (or absent)
+  // IP rows as pod intervals (ip_rows_iv_blk): a family's pods hold non-decreasing addresses in pod order
+  // ([0] IPv4, [1] IPv6), so a network less its excepts matches that family's pods in a few pod-index intervals
   bool ip_mono[2] = {false, false};
-  DevBuf ipv_tests, ipv_iv;
-  uint32_t rv_off[3] = {0, 0, 0}, Rv = 0;
-  uint32_t rpu_off[3] = {0, 0, 0};  // sub-lists of pod_peers_u: one pod peer per distinct matcher
-  DevBuf ipi_items, ipi_list;   // IP-row work items of the fused front (DIPItem; ip_rows_items_blk) and their rows
-  uint32_t ipi_off[3] = {0, 0, 0};  // items of segment x: [ipi_off[x], ipi_off[x + 1])
-  bool ip_items = false;        // the current plan's items are built (option "ip_items" on and fast IP rows present)
-  int ip_items_opt = -1;        // "ip_items": -1 auto (whole-table runs) / 0 / 1
   std::vector<DWordIP> ipw_h;   // host copy of the IP word and chunk records (ip_words)
-  DevBuf ido_grp_ns, ido_word_ns;  // identity-set namespace skip (peer_bits_blk): per row group, per identity word
-  uint32_t ido_goff[2] = {0, 0};   // first group of each direction's sub-list in ido_grp_ns
-  PeerPlan plan;                 // all pod / IP peers (host); filtered per row range
+  PeerPlan plan;                // all pod / IP peers (host); filtered per row range
+  DirDev dir[2];
+  // batched blocks (cyc_probe_prepare_blocks; pb.blocks non-empty)
+  DevBuf blk, blk_off, id_blk[2], id_win[2], first_blk;
+  uint32_t blk_wa_max = 0, blk_np_max = 0;
+  std::vector<uint64_t> blk_off_h;  // per block: plane slab offset (words), status offset (bytes); then totals
+};
+
+// What ensure_range makes for rows [lo, hi) of a partition, and that key.  A re-plan starts from
+// RangePlan{}; whatever makes the plan stale calls invalidate() (the buffers stay until the re-plan).
+struct RangePlan {
+  int64_t lo = 0, hi = 0;
+  bool src = false;  // the plan partitions sources (CYC_ROWS_SOURCE), not target rows
+  bool valid = false;
+  bool is(int64_t l, int64_t h, bool s) const { return valid && lo == l && hi == h && src == s; }
+  void invalidate() { valid = false; }
+  // plane rows per direction (ingress keyed by destination, egress by source) and the ingress word
+  // window (a source shard's sources: its peers' rows and class rows cover only those words);
+  // target-row plans: both directions [lo, hi), window [0, W)
+  int64_t rl[2] = {0, 0}, rh[2] = {0, 0};
+  uint32_t win_w0 = 0, win_wa = 0;
+  uint32_t ido_ew0 = 0, ido_ew1 = 0;  // ingress identity sets: egress-identity words of the window's sources
+  DevBuf order[2];                // emit row lists: [rows < Route::phase_split][rows >= it]
+  uint32_t phase_n1[2] = {0, 0};  // per plane: rows before the split in its emit list
   DevBuf act[2], actrec[2], sel_list;
   DevBuf arow[2];  // per identity: its first pod's row in the run's row range (in-place class rows)
   uint32_t n_act[2] = {0, 0}, n_sel = 0;
   uint32_t n_act_ph1[2] = {0, 0};  // row phases: active identities whose first row is before the split (every
                                    // phase-1 class's representative is one of them)
-  double act_targets[2] = {0, 0};  // mean namespace targets per active identity (range plan)
-  // The path decisions in effect (route.hpp), re-resolved (reroute) whenever a fact they read changes:
-  // by prepare_device, by ensure_range and by cyc_set_option — a run only reads them.
-  Route route = resolve_route(RouteIn{});
-  // Diagnostic path selectors (cyc_set_option; results never change, the GPU tests force each path;
-  // what -1 = auto chooses: resolve_route):
-  int use_graphs = -1;  // "graphs": 1 = graph replay, 2 = the same DAG enqueued eagerly on three
-                        // streams with events (no graph launch), 0 = eager on one stream with phase events
-  int ip_iv = -1;       // "ip_iv": IP rows as pod intervals where the network's family is address-monotone
-                        // in pod order (-1 auto = 1), 0 never
-  int ip_range = -1;    // "ip_range": IP rows of few, close pods from the address index: -1 auto (where the
-                        // words are not affine), 1 wherever they fit, 0 never
-  int pod_rows = -1;    // "pod_rows": pod-peer PM rows per pod directly (1), through identity outcomes
-                        // and word runs (0)
-  int member_wave = -1; // "member_wave": membership with a wave (1) or a thread (0) per identity
-  int pod_words = -1;   // "pod_words": pod-peer words in the class rows from identity sets (1, IDO),
-                        // from materialised PM rows (0)
-  int64_t class_rpb_opt = 0;  // "class_rpb": IDO class-row representatives per block; 0 = auto
-                              // (profiles/r04_class_rpb_ab.txt)
-  int step_events = 0;  // "step_events": graph / eager-DAG runs record the whole-step timing events (1);
-                        // off by default: the two timing events cost ~9 us of idle GPU per step
-                        // (config #2 0.077 -> 0.069 ms/step, profiles/r02_step_events_ab.txt)
-  int pl_wave = 1;      // "pl_wave": PM-build class rows a wave per 64-word chunk where they fit (1),
-                        // or a thread per (slot chunk, word) item (0)
-  int class_inplace = -1; // "class_inplace": fused-front class rows written straight into the output
-                          // planes (the first member pod's row), the emit copying only the others (1)
-  int pr_group = -1;   // "pr_group": sparse pod-peer rows, pod peers per block (1..64; -1 = auto)
-  int sel_lazy = -1;    // "sel_lazy": selectors evaluated where used (1) or as the dense SELRES table first (0)
-  int front_fused = 1;  // "front_fused": the front as block-range-fused launches on one stream
-                        // (build_front, launch_front), 0 = the two-branch DAG
-  int emit_interleave = -1;  // "emit_interleave": a target-row emit's row list alternates the planes'
-                             // rows (1) or is [plane 0][plane 1] (0)
-  // what the last enqueued emit launched (cyc_last_emit): kernel name(s) and launch count
-  std::string emit_kernel;
-  int emit_launches = 0;
+  double act_targets[2] = {0, 0};  // mean namespace targets per active identity
+  // the range's peers, ingress then egress sub-lists: pod peers, IP peers per pod, range-built and
+  // interval-built IP rows
+  DevBuf pod_peers, ip_peers, ip_tests, ip_ex, peer_ido, peer_row;
+  std::vector<uint32_t> prow_host;  // peer_row on the host (the panic describer reads PM / ER rows by it)
+  uint32_t Rp = 0, Ri = 0, Rr = 0, Rv = 0;
+  uint32_t rp_off[3] = {0, 0, 0}, ri_off[3] = {0, 0, 0}, rr_off[3] = {0, 0, 0}, rv_off[3] = {0, 0, 0};
+  DevBuf ipr_tests, ipr_iv, ipv_tests, ipv_iv;
+  // identity-set (IDOB) rows: the needed pod peers, one per distinct (namespace matcher, pod selector) of
+  // a direction (peer_ido maps every peer), and per row its matcher as three 16-byte records —
+  // (namespace matcher kind, namespace / selector, pod selector, 0), then the namespace selector's and
+  // the pod selector's one-requirement records (SelView::one; SEL_ALL when there is none): peer_bits_blk
+  // loads a row group's records in one vector load instead of pod_peers -> peers -> one chains
+  DevBuf pod_peers_u, pb_rec;
+  uint32_t rpu_off[3] = {0, 0, 0};
+  DevBuf ido_grp_ns, ido_word_ns;  // identity-set namespace skip (peer_bits_blk): per row group, per identity word
+  uint32_t ido_goff[2] = {0, 0};   // first group of each direction's sub-list in ido_grp_ns
+  DevBuf pp_scan, pp_post;         // sparse pod rows: pod peers scanned per word / built from postings
+  uint32_t n_scan = 0, n_post = 0;
+  uint32_t scan_off[3] = {0, 0, 0}, post_off[3] = {0, 0, 0};  // ingress peers, then egress
+  DevBuf ipi_items, ipi_list;   // IP-row work items of the fused front (DIPItem; ip_rows_items_blk) and their rows
+  uint32_t ipi_off[3] = {0, 0, 0};  // items of segment x: [ipi_off[x], ipi_off[x + 1])
+  bool ip_items = false;        // the items are built (option "ip_items" on and fast IP rows present)
+};
+
+// What a run writes (run_pipeline and what it enqueues), and the HIP handles runs reuse.  A prepare
+// resets `last` and keeps the handles.
+struct RunState {
   hipStream_t cap_stream = nullptr, cap_stream2 = nullptr, cap_stream3 = nullptr;  // graph capture branches
   hipEvent_t fork_ev = nullptr, join_ev = nullptr, sel_ev = nullptr, ports_ev = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // step and phase timing (cyc_last_timings)
+  hipEvent_t ev_p[2] = {nullptr, nullptr};  // eager runs: around phase 2's class rows
   hipGraphExec_t graph_exec = nullptr;
   hipGraph_t graph = nullptr;  // kept alive with its exec
   hipEvent_t graph_done = nullptr;  // recorded on the caller's stream after each launch of graph_exec
+  const void* graph_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   // An exec replaced by a re-capture (new output pointers, row range or tuning knob) may still have
   // a launch queued on the caller's stream: cyc_probe_run returns without synchronising.  It is
   // retired with the event recorded after its last launch and destroyed only once that event has
@@ -222,44 +229,36 @@ struct cyc_ctx {
     hipEvent_t done;  // null: never launched
   };
   std::vector<Retired> retired;
-  const void* graph_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool timed_graph = false;
-  DirDev dir[2];
-  int64_t order_lo = -1, order_hi = -1;
-  bool order_src = false;  // the range plan partitions sources (CYC_ROWS_SOURCE), not target rows
-  // the current plan: plane rows per direction (ingress keyed by destination, egress by source) and
-  // the ingress word window (a source shard's sources: its peers' rows and class rows cover only
-  // those words); target-row plans: both directions [lo, hi), window [0, W)
-  int64_t rl[2] = {0, 0}, rh[2] = {0, 0};
-  uint32_t win_w0 = 0, win_wa = 0;
-  uint32_t ido_ew0 = 0, ido_ew1 = 0;  // ingress identity sets: egress-identity words of the window's sources
-  uint32_t scan_off[3] = {0, 0, 0}, post_off[3] = {0, 0, 0};  // pp_scan / pp_post: ingress peers, then egress
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  double last_ms[3] = {0, 0, 0};
-  bool timed = false;  // the last run recorded the step timing events
-  // the IP rows' word-span records are all ~0: the last enqueued run's emit reset them (EmitArgs::reset),
-  // so the next fused front needs no fill before its IP rows (and, without a selector table, no launch A)
-  bool ip_rng_clean = false;
   bool capturing = false;  // a hipGraph capture is in progress (captured steps always fill the spans themselves)
-  bool ran = false;    // a run has been enqueued
-  hipStream_t last_stream = nullptr;  // the stream the last run was enqueued on
-  // batched blocks (cyc_probe_prepare_blocks; pb.blocks non-empty)
-  DevBuf blk, blk_off, id_blk[2], id_win[2], first_blk;
-  uint32_t blk_wa_max = 0, blk_np_max = 0;
-  std::vector<uint64_t> blk_off_h;          // per block: plane slab offset (words), status offset (bytes); then totals
-  std::vector<int> blk_rc;                  // per block status of the last run
-  std::vector<std::string> blk_msg;         // and its message
-  // Row phases ("row_phases"): a whole-table run's class rows and emit in two phases — the class rows
-  // of the classes rows [0, P/2) use, the emit of those rows, then the other classes' rows and the emit
-  // of rows [P/2, P) — so a phase's class rows (~200 MB for config #3) are still in the 256 MB MALL when
-  // its emit re-reads them; the whole table's (~400 MB) are not, and its emit reads them from HBM
-  // between its writes (round 6, profiles/r06_emit_footprint_ab.txt).  The front before the class rows
-  // runs once.
-  int row_phases = -1;     // -1 auto, 1 = off, 2 = whenever possible; Route::phase_split = the range plan's split
-                           // row (0: no phases): emit lists are [rows < split][rows >= split]
-  uint32_t phase_n1[2] = {0, 0};  // per plane: rows before the split in its emit list
-  int phase_used = 0;      // the last run's phases (2, or 0 for a plain run)
-  hipEvent_t ev_p[2] = {nullptr, nullptr};  // eager runs: around phase 2's class rows (cyc_last_timings)
+  struct Last {  // the last run of the current prepare
+    bool ran = false;    // a run has been enqueued
+    hipStream_t stream = nullptr;  // ... on this stream
+    bool timed = false;  // it recorded the step timing events
+    bool timed_graph = false;
+    int phase_used = 0;  // its row phases (2, or 0 for a plain run)
+    // what its emit launched (cyc_last_emit): kernel name(s) and launch count
+    std::string emit_kernel;
+    int emit_launches = 0;
+    std::vector<int> blk_rc;           // batched blocks: per block status
+    std::vector<std::string> blk_msg;  // and its message
+  } last;
+};
+
+struct cyc_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  bool have_policy = false, have_res = false, prepared = false;
+  PolicyIR policy;
+  Resources res;
+  Problem pb;  // of the last prepare (build_problem)
+  Options opt;
+  Prepared prep;
+  RangePlan range;
+  // The path decisions in effect (route.hpp), re-resolved (reroute) whenever a fact they read changes:
+  // by a prepare, by ensure_range and by cyc_set_option — a run only reads them.
+  Route route = resolve_route(RouteIn{});
+  RunState run;
   // multi-GPU table assembly (comm.hpp): the context's RCCL communicator, a second stream on which
   // gathered chunks are relaid out under the next chunk's all-gather, and the chunks' double buffer
   struct Comm {

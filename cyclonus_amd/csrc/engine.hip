@@ -108,12 +108,12 @@ int cyc_ctx_create(int device_id, cyc_ctx** out) {
     int cur = -1;
     bool ok = hipGetDevice(&cur) == hipSuccess && cur == device_id;
     ok = ok && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    for (auto& e : c->ev) ok = ok && hipEventCreateWithFlags(&e, EV_TIMING) == hipSuccess;
-    for (auto& e : c->ev_p) ok = ok && hipEventCreateWithFlags(&e, EV_TIMING) == hipSuccess;
+    for (auto& e : c->run.ev) ok = ok && hipEventCreateWithFlags(&e, EV_TIMING) == hipSuccess;
+    for (auto& e : c->run.ev_p) ok = ok && hipEventCreateWithFlags(&e, EV_TIMING) == hipSuccess;
     if (!ok) {  // (left to the first prepare, which reports the error)
-      for (auto& e : c->ev)
+      for (auto& e : c->run.ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
-      for (auto& e : c->ev_p)
+      for (auto& e : c->run.ev_p)
         if (e) (void)hipEventDestroy(e), e = nullptr;
       if (c->stream) (void)hipStreamDestroy(c->stream), c->stream = nullptr;
     }
@@ -131,13 +131,13 @@ void cyc_ctx_destroy(cyc_ctx* c) {
     drop_graph(c);
     reap_graphs(c, true);  // waits for each retired exec's last launch only
     destroy_events(c);
-    if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
-    if (c->cap_stream2) (void)hipStreamDestroy(c->cap_stream2);
-    if (c->cap_stream3) (void)hipStreamDestroy(c->cap_stream3);
-    if (c->sel_ev) (void)hipEventDestroy(c->sel_ev);
-    if (c->ports_ev) (void)hipEventDestroy(c->ports_ev);
-    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-    if (c->join_ev) (void)hipEventDestroy(c->join_ev);
+    if (c->run.cap_stream) (void)hipStreamDestroy(c->run.cap_stream);
+    if (c->run.cap_stream2) (void)hipStreamDestroy(c->run.cap_stream2);
+    if (c->run.cap_stream3) (void)hipStreamDestroy(c->run.cap_stream3);
+    if (c->run.sel_ev) (void)hipEventDestroy(c->run.sel_ev);
+    if (c->run.ports_ev) (void)hipEventDestroy(c->run.ports_ev);
+    if (c->run.fork_ev) (void)hipEventDestroy(c->run.fork_ev);
+    if (c->run.join_ev) (void)hipEventDestroy(c->run.join_ev);
     comm_release(c);
     (void)hipStreamDestroy(c->stream);
   }
@@ -235,8 +235,8 @@ static int probe_prepare(cyc_ctx* c, const std::function<std::vector<ProbeConfig
     clk.lap("device");
     if (!c->stream) {
       HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-      for (auto& e : c->ev) HIPCHK(hipEventCreateWithFlags(&e, EV_TIMING));
-      for (auto& e : c->ev_p) HIPCHK(hipEventCreateWithFlags(&e, EV_TIMING));
+      for (auto& e : c->run.ev) HIPCHK(hipEventCreateWithFlags(&e, EV_TIMING));
+      for (auto& e : c->run.ev_p) HIPCHK(hipEventCreateWithFlags(&e, EV_TIMING));
     }
     clk.lap("stream");
     const std::vector<ProbeConfig> probes = probes_of();
@@ -245,7 +245,12 @@ static int probe_prepare(cyc_ctx* c, const std::function<std::vector<ProbeConfig
     c->pb = build_problem(c->policy, c->res, probes, blocks);
     clk.lap("build_problem");
     drop_graph(c);
-    build_identities(c);
+    // nothing of the previous prepare, its range plan or its runs survives (the old buffers are freed
+    // before the new ones are allocated); the streams, events and retired execs do
+    c->prep = Prepared{};
+    c->range = RangePlan{};
+    c->run.last = RunState::Last{};
+    build_identities(c->pb, c->prep);
     clk.lap("identities");
     prepare_device(c);
     clk.lap("device tables");
@@ -258,15 +263,15 @@ static int probe_prepare(cyc_ctx* c, const std::function<std::vector<ProbeConfig
       shape->targets_in = int64_t(c->pb.tgt[0].size());
       shape->targets_eg = int64_t(c->pb.tgt[1].size());
       shape->peers = int64_t(c->pb.peers.size());
-      shape->classes_in = c->dir[0].n;
-      shape->classes_eg = c->dir[1].n;
+      shape->classes_in = c->prep.dir[0].n;
+      shape->classes_eg = c->prep.dir[1].n;
       shape->may_panic = c->pb.may_err ? 1 : 0;
       shape->selectors = c->pb.S;
       shape->label_sets = c->pb.L;
-      shape->pod_peers = int64_t(c->plan.pod_peers.size());
-      shape->ip_peers = int64_t(c->plan.ip_peers.size());
+      shape->pod_peers = int64_t(c->prep.plan.pod_peers.size());
+      shape->ip_peers = int64_t(c->prep.plan.ip_peers.size());
       shape->descriptors = int64_t(c->pb.descs.size());
-      shape->max_word_runs = c->plan.max_runs;
+      shape->max_word_runs = c->prep.plan.max_runs;
     }
     return (int)CYC_OK;
   });
@@ -302,28 +307,28 @@ int cyc_blocks_layout(cyc_ctx* c, int64_t* out, int64_t n) {
   if (!c->prepared || c->pb.blocks.empty()) return fail(c, CYC_ERR_ARG, "cyc_probe_prepare_blocks first");
   const size_t nb = c->pb.blocks.size();
   if (n < int64_t(nb + 1) * 2) return fail(c, CYC_ERR_ARG, "layout buffer needs 2 * (blocks + 1) entries");
-  for (size_t i = 0; i < 2 * (nb + 1); i++) out[i] = int64_t(c->blk_off_h[i]);
+  for (size_t i = 0; i < 2 * (nb + 1); i++) out[i] = int64_t(c->prep.blk_off_h[i]);
   return (int)CYC_OK;
 }
 
 int cyc_probe_run_blocks(cyc_ctx* c, void* stream, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status, int32_t* block_status) {
   if (!c) return CYC_ERR_ARG;
   if (!c->prepared || c->pb.blocks.empty()) return fail(c, CYC_ERR_ARG, "cyc_probe_prepare_blocks first");
-  const uint64_t words = c->blk_off_h[2 * c->pb.blocks.size()];
+  const uint64_t words = c->prep.blk_off_h[2 * c->pb.blocks.size()];
   if ((words && (!d_in || !d_eg)) || !d_status) return fail(c, CYC_ERR_ARG, "null output slab");
   return guarded(c, [&]() -> int {
     DeviceGuard dg(c->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = run_pipeline(c, st, d_in, d_eg, d_status, 0, c->pb.P, false, false);
     if (rc == CYC_OK && block_status)
-      for (size_t b = 0; b < c->blk_rc.size(); b++) block_status[b] = c->blk_rc[b];
+      for (size_t b = 0; b < c->run.last.blk_rc.size(); b++) block_status[b] = c->run.last.blk_rc[b];
     return rc;
   });
 }
 
 const char* cyc_block_error(const cyc_ctx* c, int64_t b) {
-  if (!c || b < 0 || size_t(b) >= c->blk_msg.size()) return "";
-  return c->blk_msg[size_t(b)].c_str();
+  if (!c || b < 0 || size_t(b) >= c->run.last.blk_msg.size()) return "";
+  return c->run.last.blk_msg[size_t(b)].c_str();
 }
 
 int cyc_probe_run_rows(cyc_ctx* c, void* stream, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status, int part, int64_t lo,
@@ -569,23 +574,23 @@ void cyc_table_destroy(cyc_table* t) {
 
 int cyc_last_timings(cyc_ctx* c, double* ms, int n) {
   if (!c || !ms) return CYC_ERR_ARG;
-  if (!c->timed) return fail(c, CYC_ERR_ARG, c->ran ? "the last run recorded no timing events (step_events = 0)" : "no run yet");
+  if (!c->run.last.timed) return fail(c, CYC_ERR_ARG, c->run.last.ran ? "the last run recorded no timing events (step_events = 0)" : "no run yet");
   return guarded(c, [&] {
     DeviceGuard dg(c->device);
-    HIPCHK(hipEventSynchronize(c->ev[3]));
+    HIPCHK(hipEventSynchronize(c->run.ev[3]));
     float a = 0, b = 0, r = 0;
-    HIPCHK(hipEventElapsedTime(&a, c->ev[0], c->ev[3]));
-    if (!c->timed_graph) {
-      HIPCHK(hipEventElapsedTime(&b, c->ev[2], c->ev[3]));
-      HIPCHK(hipEventElapsedTime(&r, c->ev[1], c->ev[2]));
-      if (c->phase_used) {  // row phases: phase 2's class rows ran between the emits (ev_p)
+    HIPCHK(hipEventElapsedTime(&a, c->run.ev[0], c->run.ev[3]));
+    if (!c->run.last.timed_graph) {
+      HIPCHK(hipEventElapsedTime(&b, c->run.ev[2], c->run.ev[3]));
+      HIPCHK(hipEventElapsedTime(&r, c->run.ev[1], c->run.ev[2]));
+      if (c->run.last.phase_used) {  // row phases: phase 2's class rows ran between the emits (ev_p)
         float p2 = 0;
-        HIPCHK(hipEventElapsedTime(&p2, c->ev_p[0], c->ev_p[1]));
+        HIPCHK(hipEventElapsedTime(&p2, c->run.ev_p[0], c->run.ev_p[1]));
         b -= p2;
         r += p2;
       }
     }
-    double v[3] = {a, c->timed_graph ? -1.0 : b, c->timed_graph ? -1.0 : r};
+    double v[3] = {a, c->run.last.timed_graph ? -1.0 : b, c->run.last.timed_graph ? -1.0 : r};
     for (int i = 0; i < n && i < 3; i++) ms[i] = v[i];
     return (int)CYC_OK;
   });
@@ -593,15 +598,15 @@ int cyc_last_timings(cyc_ctx* c, double* ms, int n) {
 
 int cyc_last_classes(cyc_ctx* c, int64_t* out, int n) {
   if (!c || !out || n < 2) return CYC_ERR_ARG;
-  if (!c->ran) return fail(c, CYC_ERR_ARG, "no run yet");
+  if (!c->run.last.ran) return fail(c, CYC_ERR_ARG, "no run yet");
   return guarded(c, [&]() -> int {
     DeviceGuard dg(c->device);
     // the last run's stream, not an event recorded after every run: an event at each step's end held
     // the next step's first launch ~4.5 us (config #2: 0.0640 -> 0.0598 ms per step without it, r05at)
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    HIPCHK(hipStreamSynchronize(c->run.last.stream));
     for (int d = 0; d < 2; d++) {
       uint32_t v[2] = {0xFFFFFFFFu, 0u};  // reps[]'s head (count - 1) and tail (row phases' phase-2 classes)
-      if (c->dir[d].n && c->n_act[d]) HIPCHK(hipMemcpy(v, c->dir[d].rep_cnt(), 8, hipMemcpyDeviceToHost));
+      if (c->prep.dir[d].n && c->range.n_act[d]) HIPCHK(hipMemcpy(v, c->prep.dir[d].rep_cnt(), 8, hipMemcpyDeviceToHost));
       out[d] = int64_t(uint32_t(v[0] + 1u)) + int64_t(v[1]);
     }
     return (int)CYC_OK;
@@ -610,13 +615,13 @@ int cyc_last_classes(cyc_ctx* c, int64_t* out, int n) {
 
 int cyc_last_emit(cyc_ctx* c, char* name, size_t cap, int64_t* launches) {
   if (!c) return CYC_ERR_ARG;
-  if (!c->ran) return fail(c, CYC_ERR_ARG, "no run yet");
+  if (!c->run.last.ran) return fail(c, CYC_ERR_ARG, "no run yet");
   if (name && cap) {
-    const size_t n = std::min(cap - 1, c->emit_kernel.size());
-    std::memcpy(name, c->emit_kernel.data(), n);
+    const size_t n = std::min(cap - 1, c->run.last.emit_kernel.size());
+    std::memcpy(name, c->run.last.emit_kernel.data(), n);
     name[n] = 0;
   }
-  if (launches) *launches = c->emit_launches;
+  if (launches) *launches = c->run.last.emit_launches;
   return CYC_OK;
 }
 
@@ -625,51 +630,19 @@ int cyc_set_option(cyc_ctx* c, const char* name, int64_t value) {
   std::unique_ptr<DeviceGuard> dg;
   if (c->stream) dg.reset(new DeviceGuard(c->device, false));  // drop_graph may destroy this context's execs
   const std::string n(name);
-  auto range = [&](int64_t lo, int64_t hi) {
-    if (value < lo || value > hi) throw Panic{CYC_ERR_ARG, n + " must be in " + std::to_string(lo) + ".." + std::to_string(hi)};
-  };
   return guarded(c, [&]() -> int {
-    if (n == "graphs") range(-1, 2), c->use_graphs = int(value);
-    else if (n == "front_fused") range(0, 1), c->front_fused = int(value);
-    else if (n == "pod_words") range(-1, 1), c->pod_words = int(value);
-    else if (n == "pod_rows") range(-1, 1), c->pod_rows = int(value);
-    else if (n == "ip_range") {
-      range(-1, 1);
-      c->ip_range = int(value);
-      c->order_lo = c->order_hi = -1;  // the next run re-plans which IP rows are range-built
+    const OptionRow* o = find_option(name);
+    if (!o) return fail(c, CYC_ERR_ARG, "unknown option " + n);
+    if (value < o->lo || value > o->hi)
+      throw Panic{CYC_ERR_ARG, n + " must be in " + std::to_string(o->lo) + ".." + std::to_string(o->hi)};
+    if (n == "row_phases" && (value == 0 || value > 2)) throw Panic{CYC_ERR_ARG, "row_phases must be -1 (auto), 1 (off) or 2"};
+    c->opt.*o->field = n == "pr_group" && value == 0 ? -1 : int(value);
+    if (o->stale == Stale::range_plan) c->range.invalidate();  // the next run re-plans
+    if (o->stale == Stale::plvt) {  // rebuilt (or not) by the next run
+      c->prep.plvt_ready = false;
+      c->prep.plvt.alloc(0);
     }
-    else if (n == "ip_iv") {
-      range(-1, 1);
-      c->ip_iv = int(value);
-      c->order_lo = c->order_hi = -1;  // the next run re-plans which IP rows are interval-built
-    }
-    else if (n == "member_wave") range(-1, 1), c->member_wave = int(value);
-    else if (n == "class_rpb") range(0, 64), c->class_rpb_opt = value;
-    else if (n == "pl_wave") range(0, 1), c->pl_wave = int(value);
-    else if (n == "sel_lazy") range(-1, 1), c->sel_lazy = int(value);
-    else if (n == "pr_group") range(-1, 64), c->pr_group = int(value == 0 ? -1 : value);
-    else if (n == "class_inplace") range(-1, 1), c->class_inplace = int(value);
-    else if (n == "step_events") range(0, 1), c->step_events = int(value);
-    else if (n == "emit_interleave") range(-1, 1), c->emit_interleave = int(value);
-    else if (n == "row_phases") {
-      range(-1, 4);
-      if (value == 0 || value > 2) throw Panic{CYC_ERR_ARG, "row_phases must be -1 (auto), 1 (off) or 2"};
-      c->row_phases = int(value);
-      c->order_lo = c->order_hi = -1;  // the emit lists are re-planned
-    }
-    else if (n == "ip_items") {
-      range(-1, 1);
-      c->ip_items_opt = int(value);
-      c->order_lo = c->order_hi = -1;  // the next run re-plans the items
-    }
-    else if (n == "plvt_max_mb") {
-      range(0, 1 << 20);
-      c->plvt_max_mb = value;
-      c->plvt_ready = false;  // rebuilt (or not) by the next run
-      c->plvt.alloc(0);
-    }
-    else return fail(c, CYC_ERR_ARG, "unknown option " + n);
-    reroute(c);  // (the range plan reads no option it does not invalidate above: the route alone is re-resolved)
+    reroute(c);
     drop_graph(c);
     return (int)CYC_OK;
   });
@@ -678,38 +651,23 @@ int cyc_set_option(cyc_ctx* c, const char* name, int64_t value) {
 int cyc_get_option(cyc_ctx* c, const char* name, int64_t* value) {
   if (!c || !name || !value) return CYC_ERR_ARG;
   const std::string n(name);
-  if (n == "graphs") *value = c->use_graphs;
-  else if (n == "front_fused") *value = c->front_fused;
-  else if (n == "pod_rows") *value = c->pod_rows;
-  else if (n == "ip_range") *value = c->ip_range;
-  else if (n == "ip_iv") *value = c->ip_iv;
-  else if (n == "ip_iv_rows") *value = c->Rv;  // (the last range plan's interval-built rows)
-  else if (n == "member_wave") *value = c->member_wave;
-  else if (n == "class_rpb") *value = c->class_rpb_opt;
-  else if (n == "pl_wave") *value = c->pl_wave;
-  else if (n == "sel_lazy") *value = c->sel_lazy;
-  else if (n == "pr_group") *value = c->pr_group;
-  else if (n == "class_inplace") *value = c->class_inplace;
-  else if (n == "row_phases") *value = c->row_phases;
-  else if (n == "row_phases_active") *value = c->phase_used;  // (the last run's phases; 0: a plain run)
-  else if (n == "class_inplace_active") {
-    if (!c->prepared || c->order_lo < 0) return fail(c, CYC_ERR_ARG, "class_inplace_active: run a probe first");
-    *value = c->route.inplace ? 1 : 0;
-  }
-  else if (n == "step_events") *value = c->step_events;
-  else if (n == "emit_interleave") *value = c->emit_interleave;
-  else if (n == "ip_items") *value = c->ip_items_opt;
-  else if (n == "plvt_max_mb") *value = c->plvt_max_mb;
-  else if (n == "plvt_active") *value = c->plvt_ready ? 1 : 0;
-  else if (n == "pl_wave_active") {
-    if (!c->prepared) return fail(c, CYC_ERR_ARG, "pl_wave_active: call cyc_probe_prepare first");
-    *value = c->route.pl_wave ? 1 : 0;
-  } else if (n == "launch") *value = c->route.launch;  // in effect
-  else if (n == "front_fused_active") *value = c->route.fused ? 1 : 0;
-  else if (n == "pod_words") {
-    if (!c->prepared) return fail(c, CYC_ERR_ARG, "pod_words: call cyc_probe_prepare first");
+  auto need_prepare = [&] { return fail(c, CYC_ERR_ARG, n + ": call cyc_probe_prepare first"); };
+  if (n == "pod_words") {  // the mode in effect, not the option
+    if (!c->prepared) return need_prepare();
     *value = c->route.ido ? 1 : 0;
-  } else return fail(c, CYC_ERR_ARG, std::string("unknown option ") + name);
+  } else if (const OptionRow* o = find_option(name)) *value = c->opt.*o->field;
+  else if (n == "launch") *value = c->route.launch;  // in effect
+  else if (n == "front_fused_active") *value = c->route.fused ? 1 : 0;
+  else if (n == "pl_wave_active") {
+    if (!c->prepared) return need_prepare();
+    *value = c->route.pl_wave ? 1 : 0;
+  } else if (n == "class_inplace_active") {
+    if (!c->prepared || !c->range.valid) return fail(c, CYC_ERR_ARG, "class_inplace_active: run a probe first");
+    *value = c->route.inplace ? 1 : 0;
+  } else if (n == "plvt_active") *value = c->prep.plvt_ready ? 1 : 0;
+  else if (n == "ip_iv_rows") *value = c->range.Rv;  // (the last range plan's interval-built rows)
+  else if (n == "row_phases_active") *value = c->run.last.phase_used;  // (the last run's phases; 0: a plain run)
+  else return fail(c, CYC_ERR_ARG, "unknown option " + n);
   return (int)CYC_OK;
 }
 

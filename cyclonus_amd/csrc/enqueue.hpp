@@ -10,33 +10,36 @@ enum { COMMON_SELECTORS = 1, COMMON_PORTS = 2, COMMON_FILL = 4, COMMON_ALL = 7 }
 
 static void enq_common(cyc_ctx* c, hipStream_t st, int parts = COMMON_ALL) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
   const uint32_t P = pb.P, K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
   const uint32_t M = uint32_t(pb.pms.size());
-  if ((parts & COMMON_FILL) && !pb.may_err && (c->Ri || c->Rr))  // IP-peer word spans (k_ip_rows_fast)
-    k_fill_u32<<<grid1(c->pb.peers.size() * 4, 256), 256, 0, st>>>(c->ip_rng.as<uint32_t>(), c->pb.peers.size() * 4, 0xFFFFFFFFu);
+  if ((parts & COMMON_FILL) && !pb.may_err && (rp.Ri || rp.Rr))  // IP-peer word spans (k_ip_rows_fast)
+    k_fill_u32<<<grid1(pb.peers.size() * 4, 256), 256, 0, st>>>(prep.ip_rng.as<uint32_t>(), pb.peers.size() * 4, 0xFFFFFFFFu);
   if (!(parts & COMMON_SELECTORS)) goto ports;
   // 1. selectors x label sets
-  if (uint64_t(c->n_sel) * pb.L && c->dense_sel)
-    k_selectors_dense<<<unsigned(uint64_t(c->n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))), 256, 0, st>>>(
-        c->n_sel, pb.L, c->sel_off.as<uint32_t>(), c->dreqs.as<DReq>(), c->req_vals.as<uint32_t>(), c->lvt.as<uint32_t>(),
-        c->selres.as<uint8_t>(), c->sel_list.as<uint32_t>());
-  else if (uint64_t(c->n_sel) * pb.L)
-    k_selectors<<<grid1(uint64_t(c->n_sel) * pb.L, 256), 256, 0, st>>>(
-        c->n_sel, pb.L, c->sel_off.as<uint32_t>(), c->reqs.as<DReq>(), c->req_vals.as<uint32_t>(), c->ls_off.as<uint32_t>(),
-        c->ls_key.as<uint32_t>(), c->ls_val.as<uint32_t>(), c->selres.as<uint8_t>(), c->sel_list.as<uint32_t>());
+  if (uint64_t(rp.n_sel) * pb.L && prep.dense_sel)
+    k_selectors_dense<<<unsigned(uint64_t(rp.n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))), 256, 0, st>>>(
+        rp.n_sel, pb.L, prep.sel_off.as<uint32_t>(), prep.dreqs.as<DReq>(), prep.req_vals.as<uint32_t>(), prep.lvt.as<uint32_t>(),
+        prep.selres.as<uint8_t>(), rp.sel_list.as<uint32_t>());
+  else if (uint64_t(rp.n_sel) * pb.L)
+    k_selectors<<<grid1(uint64_t(rp.n_sel) * pb.L, 256), 256, 0, st>>>(
+        rp.n_sel, pb.L, prep.sel_off.as<uint32_t>(), prep.reqs.as<DReq>(), prep.req_vals.as<uint32_t>(),
+        prep.ls_off.as<uint32_t>(), prep.ls_key.as<uint32_t>(), prep.ls_val.as<uint32_t>(), prep.selres.as<uint8_t>(),
+        rp.sel_list.as<uint32_t>());
 ports:
   if (!(parts & COMMON_PORTS)) return;
   // 3. port matchers x job descriptors
   if (M && pb.descs.size())
-    k_portok<<<grid1(uint64_t(M) * D, 256), 256, 0, st>>>(M, D, c->pms.as<DPortM>(), c->pents.as<DPortEntry>(),
-                                                          c->descs.as<DDesc>(), c->portok.as<uint8_t>());
+    k_portok<<<grid1(uint64_t(M) * D, 256), 256, 0, st>>>(M, D, prep.pms.as<DPortM>(), prep.pents.as<DPortEntry>(),
+                                                          prep.descs.as<DDesc>(), prep.portok.as<uint8_t>());
   if (M && pb.descs.size() && c->route.port_bits)
-    k_portbits<<<(M + 255) / 256, 256, 0, st>>>(M, D, c->portok.as<uint8_t>(), c->portbits.as<uint32_t>());
+    k_portbits<<<(M + 255) / 256, 256, 0, st>>>(M, D, prep.portok.as<uint8_t>(), prep.portbits.as<uint32_t>());
   // 4. per-slot destination words
   if (uint64_t(K) * W)
     k_slot_words<<<unsigned((uint64_t(K) * W + 3) / 4), 256, 0, st>>>(
-        P, K, W, D, c->slot_desc.as<int32_t>(), c->slot_status.as<uint8_t>(), c->VALID.as<uint64_t>(),
-        c->DESCW.as<int32_t>(), c->DM.as<uint64_t>());
+        P, K, W, D, prep.slot_desc.as<int32_t>(), prep.slot_status.as<uint8_t>(), prep.VALID.as<uint64_t>(),
+        prep.DESCW.as<int32_t>(), prep.DM.as<uint64_t>());
 }
 
 // 2. peer rows of direction d's peers: pod peers in identity space, expanded over word runs
@@ -44,8 +47,12 @@ ports:
 enum { PEERS_POD = 1, PEERS_IP = 2 };
 static void enq_peer_rows(cyc_ctx* c, int d, hipStream_t st, int which = PEERS_POD | PEERS_IP) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
   const uint32_t P = pb.P, W = pb.W;
-  const uint32_t E = c->dir[1].n;
+  const uint32_t E = prep.dir[1].n;
+  uint64_t *PM = prep.PM.as<uint64_t>(), *ER = prep.ER.as<uint64_t>();
+  const uint32_t *id_ns = prep.dir[1].id_ns.as<uint32_t>(), *id_ls = prep.dir[1].id_ls.as<uint32_t>();  // egress identities
   // d = 2: both directions in one launch (their peer sub-lists are adjacent) when they share a window
   if (d == 2 && !c->route.one_window) {
     enq_peer_rows(c, 0, st, which);
@@ -54,97 +61,92 @@ static void enq_peer_rows(cyc_ctx* c, int d, hipStream_t st, int which = PEERS_P
   }
   const int dlo = d == 2 ? 0 : d, dhi = d == 2 ? 2 : d + 1;
   uint32_t w0, nw, c0, nch;  // the rows' word window (a source shard's ingress peers: its sources' words)
-  peer_window(c, d == 2 ? 1 : d, w0, nw);
-  peer_chunks(c, d == 2 ? 1 : d, c0, nch);
-  const uint32_t r0 = c->rp_off[dlo], Rp = (which & PEERS_POD) ? c->rp_off[dhi] - r0 : 0u;
+  peer_window(rp, W, d == 2 ? 1 : d, w0, nw);
+  peer_chunks(rp, W, d == 2 ? 1 : d, c0, nch);
+  const uint32_t r0 = rp.rp_off[dlo], Rp = (which & PEERS_POD) ? rp.rp_off[dhi] - r0 : 0u;
   if (Rp && E && W && c->route.ido) {
     const uint32_t EW = (E + 63) / 64;
     for (int x = dlo; x < dhi; x++) {  // per direction: its identity word window
-      const uint32_t u0 = c->rpu_off[x], Ru = c->rpu_off[x + 1] - u0;  // distinct matchers only
-      const uint32_t ew0 = x == 0 ? c->ido_ew0 : 0u, new_ = x == 0 ? c->ido_ew1 - c->ido_ew0 : EW;
+      const uint32_t u0 = rp.rpu_off[x], Ru = rp.rpu_off[x + 1] - u0;  // distinct matchers only
+      const uint32_t ew0 = x == 0 ? rp.ido_ew0 : 0u, new_ = x == 0 ? rp.ido_ew1 - rp.ido_ew0 : EW;
       if (Ru && new_)
         k_peer_bits<<<unsigned((uint64_t((Ru + PB_GROUP - 1) / PB_GROUP) * new_ + 3) / 4), 256, 0, st>>>(
-            Ru, E, EW, c->pod_peers_u.as<uint32_t>() + u0, c->peers.as<DPeer>(), c->selres.as<uint8_t>(), pb.L,
-            c->dir[1].id_ns.as<uint32_t>(), c->id_nsls.as<uint32_t>(), c->dir[1].id_ls.as<uint32_t>(),
-            c->idob.as<uint64_t>() + uint64_t(u0) * EW, ew0, new_, c->ido_grp_ns.as<uint2>() + c->ido_goff[x],
-            c->ido_word_ns.as<uint2>());
+            Ru, E, EW, rp.pod_peers_u.as<uint32_t>() + u0, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(), pb.L,
+            id_ns, prep.id_nsls.as<uint32_t>(), id_ls, prep.idob.as<uint64_t>() + uint64_t(u0) * EW, ew0, new_,
+            rp.ido_grp_ns.as<uint2>() + rp.ido_goff[x], rp.ido_word_ns.as<uint2>());
     }
   } else if (Rp && E && nw && c->route.pod_direct) {
-    const uint32_t* plist = c->pod_peers.as<uint32_t>() + r0;
+    const uint32_t* plist = rp.pod_peers.as<uint32_t>() + r0;
     const unsigned g = unsigned((pod_direct_waves(Rp, nw) + 3) / 4);
-    const uint32_t* eid = c->dir[1].pod_id.as<uint32_t>();
+    const uint32_t* eid = prep.dir[1].pod_id.as<uint32_t>();
     if (pb.may_err)
-      k_pod_rows_direct<true><<<g, 256, 0, st>>>(Rp, P, W, plist, c->peers.as<DPeer>(), c->selres.as<uint8_t>(), pb.L, eid,
-                                                 c->dir[1].id_ns.as<uint32_t>(), c->id_nsls.as<uint32_t>(),
-                                                 c->dir[1].id_ls.as<uint32_t>(), c->PM.as<uint64_t>(), c->ER.as<uint64_t>(), w0, nw);
+      k_pod_rows_direct<true><<<g, 256, 0, st>>>(Rp, P, W, plist, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(), pb.L, eid,
+                                                 id_ns, prep.id_nsls.as<uint32_t>(), id_ls, PM, ER, w0, nw);
     else
-      k_pod_rows_direct<false><<<g, 256, 0, st>>>(Rp, P, W, plist, c->peers.as<DPeer>(), c->selres.as<uint8_t>(), pb.L, eid,
-                                                  c->dir[1].id_ns.as<uint32_t>(), c->id_nsls.as<uint32_t>(),
-                                                  c->dir[1].id_ls.as<uint32_t>(), c->PM.as<uint64_t>(), c->ER.as<uint64_t>(), w0, nw);
+      k_pod_rows_direct<false><<<g, 256, 0, st>>>(Rp, P, W, plist, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(), pb.L, eid,
+                                                  id_ns, prep.id_nsls.as<uint32_t>(), id_ls, PM, ER, w0, nw);
   } else if (Rp && E && nw) {
-    const uint32_t* plist = c->pod_peers.as<uint32_t>() + r0;
-    uint8_t* ido = c->ido.as<uint8_t>() + uint64_t(r0) * E;
-    k_peer_ident<<<grid1(uint64_t(Rp) * E, 256), 256, 0, st>>>(Rp, E, plist, c->peers.as<DPeer>(), c->selres.as<uint8_t>(),
-                                                               pb.L, c->dir[1].id_ns.as<uint32_t>(),
-                                                               c->id_nsls.as<uint32_t>(), c->dir[1].id_ls.as<uint32_t>(), ido);
+    const uint32_t* plist = rp.pod_peers.as<uint32_t>() + r0;
+    uint8_t* ido = prep.ido.as<uint8_t>() + uint64_t(r0) * E;
+    k_peer_ident<<<grid1(uint64_t(Rp) * E, 256), 256, 0, st>>>(Rp, E, plist, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(),
+                                                               pb.L, id_ns, prep.id_nsls.as<uint32_t>(), id_ls, ido);
     unsigned g = unsigned(uint64_t((nw + 255) / 256) * Rp);
     if (pb.may_err)
-      k_pod_rows<true><<<g, 256, 0, st>>>(Rp, E, W, plist, ido, c->word_off.as<uint32_t>(), c->run_e.as<uint32_t>(),
-                                          c->run_mask.as<uint64_t>(), c->PM.as<uint64_t>(), c->ER.as<uint64_t>(), w0, nw);
+      k_pod_rows<true><<<g, 256, 0, st>>>(Rp, E, W, plist, ido, prep.word_off.as<uint32_t>(), prep.run_e.as<uint32_t>(),
+                                          prep.run_mask.as<uint64_t>(), PM, ER, w0, nw);
     else
-      k_pod_rows<false><<<g, 256, 0, st>>>(Rp, E, W, plist, ido, c->word_off.as<uint32_t>(), c->run_e.as<uint32_t>(),
-                                           c->run_mask.as<uint64_t>(), c->PM.as<uint64_t>(), c->ER.as<uint64_t>(), w0, nw);
+      k_pod_rows<false><<<g, 256, 0, st>>>(Rp, E, W, plist, ido, prep.word_off.as<uint32_t>(), prep.run_e.as<uint32_t>(),
+                                           prep.run_mask.as<uint64_t>(), PM, ER, w0, nw);
   }
-  const uint32_t v0 = c->rv_off[dlo], Rv = (which & PEERS_IP) ? c->rv_off[dhi] - v0 : 0u;
+  const uint32_t v0 = rp.rv_off[dlo], Rv = (which & PEERS_IP) ? rp.rv_off[dhi] - v0 : 0u;
   if (Rv && nw)
-    k_ip_rows_iv<<<(Rv + 3) / 4, 256, 0, st>>>(Rv, W, c->ipv_tests.as<DIPIv>() + v0, c->ipv_iv.as<uint2>(),
-                                             c->ip_words.as<DWordIP>(), c->PM.as<uint64_t>(), c->ip_rng.as<uint32_t>(), ip_cnz(c),
-                                             c0, nch);
-  const uint32_t q0 = c->rr_off[dlo], Rr = (which & PEERS_IP) ? c->rr_off[dhi] - q0 : 0u;
+    k_ip_rows_iv<<<(Rv + 3) / 4, 256, 0, st>>>(Rv, W, rp.ipv_tests.as<DIPIv>() + v0, rp.ipv_iv.as<uint2>(),
+                                             prep.ip_words.as<DWordIP>(), PM, prep.ip_rng.as<uint32_t>(), ip_cnz(c), c0, nch);
+  const uint32_t q0 = rp.rr_off[dlo], Rr = (which & PEERS_IP) ? rp.rr_off[dhi] - q0 : 0u;
   if (Rr && nw)
-    k_ip_rows_range<<<(Rr + 3) / 4, 256, 0, st>>>(Rr, W, c->ipr_tests.as<DIPRange>() + q0, c->ipr_iv.as<uint2>(),
-                                                c->ipsort.as<uint32_t>(), c->PM.as<uint64_t>(), c->ip_rng.as<uint32_t>(), ip_cnz(c), c0, nch);
-  const uint32_t i0 = c->ri_off[dlo], Ri = (which & PEERS_IP) ? c->ri_off[dhi] - i0 : 0u;
+    k_ip_rows_range<<<(Rr + 3) / 4, 256, 0, st>>>(Rr, W, rp.ipr_tests.as<DIPRange>() + q0, rp.ipr_iv.as<uint2>(),
+                                                prep.ipsort.as<uint32_t>(), PM, prep.ip_rng.as<uint32_t>(), ip_cnz(c), c0, nch);
+  const uint32_t i0 = rp.ri_off[dlo], Ri = (which & PEERS_IP) ? rp.ri_off[dhi] - i0 : 0u;
   if (Ri && nw) {
-    const DIPTest* tests = c->ip_tests.as<DIPTest>() + i0;
+    const DIPTest* tests = rp.ip_tests.as<DIPTest>() + i0;
     if (pb.may_err) {
       // batch size: as many peers per block as keep >= ~2048 blocks in flight, at most IPB_BATCH
       const uint64_t wch = (nw + 3) / 4;
       const uint64_t nb_want = (2048 + wch - 1) / wch;
       const uint32_t bat = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(IPB_BATCH, (Ri + nb_want - 1) / nb_want)));
       unsigned g = unsigned(wch * ((Ri + bat - 1) / bat));
-      k_ip_rows<true><<<g, 256, 0, st>>>(Ri, P, W, tests, c->ip_ex.as<DCidr>(), c->pod_ip.as<DIP>(), c->PM.as<uint64_t>(),
-                                         c->ER.as<uint64_t>(), bat, w0, nw);
+      k_ip_rows<true><<<g, 256, 0, st>>>(Ri, P, W, tests, rp.ip_ex.as<DCidr>(), prep.pod_ip.as<DIP>(), PM,
+                                         ER, bat, w0, nw);
     } else {
       const uint32_t grp = IP_GROUP;
       k_ip_rows_fast<<<unsigned(ip_rows_blocks(Ri, nch, grp)), 256, 0, st>>>(
-          Ri, P, W, tests, c->ip_ex.as<DCidr>(), c->pod_ip.as<DIP>(), c->ip_words.as<DWordIP>(), c->PM.as<uint64_t>(),
-          c->ip_rng.as<uint32_t>(), ip_cnz(c), grp, c0, nch);
+          Ri, P, W, tests, rp.ip_ex.as<DCidr>(), prep.pod_ip.as<DIP>(), prep.ip_words.as<DWordIP>(), PM,
+          prep.ip_rng.as<uint32_t>(), ip_cnz(c), grp, c0, nch);
     }
   }
 }
 
 // 5. membership + classes of direction d
 static void enq_member_clear(cyc_ctx* c, int d, hipStream_t st) {
-  DirDev& dd = c->dir[d];
+  DirDev& dd = c->prep.dir[d];
   if (dd.n) HIPCHK(hipMemsetAsync(dd.ht_key.p, 0xFF, dd.ht_key.bytes, st));  // keys and reps: one buffer
 }
 
 // The class rows of a run empty the hash table for the next one (ht_clear_slice); only runs whose
 // class rows do not launch (no slots or no pods) need the memset (prepare_device empties it once).
 static bool class_rows_clear_ht(const cyc_ctx* c, int d) {
-  return c->dir[d].n && c->pb.K && c->pb.W && c->n_act[d];
+  return c->prep.dir[d].n && c->pb.K && c->pb.W && c->range.n_act[d];
 }
 
 static void enq_member(cyc_ctx* c, int d, hipStream_t st, bool clear = true) {
-  DirDev& dd = c->dir[d];
+  DirDev& dd = c->prep.dir[d];
   if (!dd.n) return;
   if (clear && !class_rows_clear_ht(c, d)) enq_member_clear(c, d, st);
   MemberArgs ma = member_args(c, d);
-  if (!c->n_act[d]) return;
-  if (c->route.member_wave[d]) k_member_wave<<<unsigned((uint64_t(c->n_act[d]) + 3) / 4), 256, 0, st>>>(ma);
-  else k_member<<<grid1(c->n_act[d], 128), 128, 0, st>>>(ma);
-  k_classify<<<grid1(c->n_act[d], 256), 256, 0, st>>>(ma, dd.class_of.as<uint32_t>());
+  if (!c->range.n_act[d]) return;
+  if (c->route.member_wave[d]) k_member_wave<<<unsigned((uint64_t(c->range.n_act[d]) + 3) / 4), 256, 0, st>>>(ma);
+  else k_member<<<grid1(c->range.n_act[d], 128), 128, 0, st>>>(ma);
+  k_classify<<<grid1(c->range.n_act[d], 256), 256, 0, st>>>(ma, dd.class_of.as<uint32_t>());
 }
 
 #ifndef CYC_PHASE_GRID
@@ -159,7 +161,7 @@ static void enq_member(cyc_ctx* c, int d, hipStream_t st, bool clear = true) {
 // the fused front, build_front), as many as fit the staged identity-set budget
 static uint32_t class_rpb(const cyc_ctx* c, size_t per_rep_lds, uint32_t want = 0) {
   const uint64_t fit = std::max<uint64_t>(1, IDO_LDS_BYTES / std::max<size_t>(per_rep_lds, 1));
-  const int64_t w = want ? int64_t(want) : c->class_rpb_opt ? c->class_rpb_opt : 4;
+  const int64_t w = want ? int64_t(want) : c->opt.class_rpb ? c->opt.class_rpb : 4;
   return uint32_t(std::max<int64_t>(1, std::min<int64_t>(w, int64_t(fit))));
 }
 // ... their LDS bytes per representative: set_rows identity sets (KC slot rows, or D descriptor rows)
@@ -171,26 +173,28 @@ static uint64_t ido_row_blocks(uint32_t WA, uint32_t K, uint32_t KC, uint32_t re
 
 static RowArgs row_args(cyc_ctx* c, int d) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
   const uint32_t P = pb.P, K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
-  DirDev& dd = c->dir[d];
+  DirDev& dd = prep.dir[d];
   RowArgs ra{};
   ra.tgt = dd.tgt.as<DTarget>();
-  ra.peers = c->peers.as<DPeer>();
-  ra.PM = c->PM.as<uint64_t>();
-  ra.ER = c->ER.as<uint64_t>();
-  ra.portok = c->portok.as<uint8_t>();
+  ra.peers = prep.peers.as<DPeer>();
+  ra.PM = prep.PM.as<uint64_t>();
+  ra.ER = prep.ER.as<uint64_t>();
+  ra.portok = prep.portok.as<uint8_t>();
   // descriptor bit rows of the port table (k_portbits; computed whenever D <= 32)
-  ra.portbits = c->route.port_bits && pb.pms.size() && pb.descs.size() ? c->portbits.as<uint32_t>() : nullptr;
+  ra.portbits = c->route.port_bits && pb.pms.size() && pb.descs.size() ? prep.portbits.as<uint32_t>() : nullptr;
   ra.D = D;
   ra.n_ident = dd.n;
   ra.K = K;
   ra.W = W;
   ra.P = P;
-  peer_window(c, d, ra.w0, ra.WA);  // the class rows cover their peers' word window
+  peer_window(c->range, c->pb.W, d, ra.w0, ra.WA);  // the class rows cover their peers' word window
   if (!c->pb.blocks.empty()) {     // batched blocks: each class row covers its block's words
     ra.w0 = 0;
-    ra.WA = c->blk_wa_max;
-    ra.id_win = c->id_win[d].as<uint2>();
+    ra.WA = prep.blk_wa_max;
+    ra.id_win = prep.id_win[d].as<uint2>();
   }
   ra.class_of = dd.class_of.as<uint32_t>();
   ra.cnt = dd.cnt.as<uint32_t>();
@@ -199,29 +203,29 @@ static RowArgs row_args(cyc_ctx* c, int d) {
   ra.id_err = dd.err.as<uint8_t>();
   ra.id_desc = dd.id_desc.as<int32_t>();
   ra.id_status = dd.id_status.as<uint8_t>();
-  ra.VALID = c->VALID.as<uint64_t>();
-  ra.DESCW = c->DESCW.as<int32_t>();
-  ra.DM = c->DM.as<uint64_t>();
+  ra.VALID = prep.VALID.as<uint64_t>();
+  ra.DESCW = prep.DESCW.as<int32_t>();
+  ra.DM = prep.DM.as<uint64_t>();
   ra.A = dd.A.as<uint64_t>();
   ra.AE = pb.may_err ? dd.AE.as<uint64_t>() : nullptr;
-  ra.rep_blocks = c->n_act[d];  // k_class_rows (panic path): a block row per representative slot
+  ra.rep_blocks = rp.n_act[d];  // k_class_rows (panic path): a block row per representative slot
   ra.reps = dd.reps.as<uint32_t>();
   ra.rep_cnt = dd.rep_cnt();
-  ra.IDOB = c->idob.as<uint64_t>();
-  ra.peer_ido = c->peer_ido.as<uint32_t>();
-  ra.prow = c->peer_row.as<uint32_t>();
-  ra.zero = c->zeros.as<uint64_t>();
-  ra.runs = c->runs.as<WordRuns>();
+  ra.IDOB = prep.idob.as<uint64_t>();
+  ra.peer_ido = rp.peer_ido.as<uint32_t>();
+  ra.prow = rp.peer_row.as<uint32_t>();
+  ra.zero = prep.zeros.as<uint64_t>();
+  ra.runs = prep.runs.as<WordRuns>();
   ra.B = dd.B.as<uint64_t>();
   ra.ip_off = dd.ip_off.as<uint32_t>();
   ra.ip_cnt = dd.ip_cnt.as<uint32_t>();
   ra.ip_list = dd.ip_list.as<uint4>();
-  ra.ip_rng = c->ip_rng.as<uint32_t>();
+  ra.ip_rng = prep.ip_rng.as<uint32_t>();
   ra.ip_cnz = ip_cnz(c);
-  ra.E = c->dir[1].n;
+  ra.E = prep.dir[1].n;
   ra.EW = (ra.E + 63) / 64;
-  ra.ew_lo = d == 0 ? c->ido_ew0 : 0u;
-  ra.ew_hi = d == 0 ? c->ido_ew1 : ra.EW;
+  ra.ew_lo = d == 0 ? rp.ido_ew0 : 0u;
+  ra.ew_hi = d == 0 ? rp.ido_ew1 : ra.EW;
   ra.NB = d == 0 ? K : D;
   // the first kernel below empties the hash table for the next run (keys + reps; not the counter)
   ra.ht_clear = reinterpret_cast<uint32_t*>(dd.ht_key.p);
@@ -232,9 +236,11 @@ static RowArgs row_args(cyc_ctx* c, int d) {
 
 static void enq_class_rows(cyc_ctx* c, int d, hipStream_t st) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
   const uint32_t K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
-  DirDev& dd = c->dir[d];
-  if (!dd.n || !K || !W || !c->n_act[d]) return;
+  DirDev& dd = prep.dir[d];
+  if (!dd.n || !K || !W || !rp.n_act[d]) return;
   RowArgs ra = row_args(c, d);
   if (!ra.WA) return;
   if (pb.may_err) {  // the ordered walk with panic bits: one block row per identity, 8 slots per thread
@@ -243,13 +249,13 @@ static void enq_class_rows(cyc_ctx* c, int d, hipStream_t st) {
     else k_class_rows<true><<<g, 256, 0, st>>>(ra);
   } else if (c->route.ido) {
     // identity sets first (one wave per representative and 4 slots / descriptors), then the rows
-    const uint64_t waves = uint64_t(c->n_act[d]) * ((ra.NB + CI_G - 1) / CI_G);
+    const uint64_t waves = uint64_t(rp.n_act[d]) * ((ra.NB + CI_G - 1) / CI_G);
     if (d == 0) k_class_ident<false, CI_G><<<unsigned((waves + 3) / 4), 256, 0, st>>>(ra);
     else k_class_ident<true, CI_G><<<unsigned((waves + 3) / 4), 256, 0, st>>>(ra);
     ra.ht_clear_words = 0;
     const size_t per = ido_rep_lds(d == 0 ? 4u : D, ra.EW);  // (class_rows_ido_blk stages KC = 4 slot rows, or D descriptor rows)
     ra.rpb = class_rpb(c, per);
-    const unsigned gi = unsigned(ido_row_blocks(ra.WA, K, 4, c->n_act[d], ra.rpb));
+    const unsigned gi = unsigned(ido_row_blocks(ra.WA, K, 4, rp.n_act[d], ra.rpb));
     if (d == 0) k_class_rows_ido<false, 4><<<gi, 256, per * ra.rpb, st>>>(ra);
     else k_class_rows_ido<true, 4><<<gi, 256, per * ra.rpb, st>>>(ra);
   } else {  // per-class flattened peer lists (the IP word spans are final here)
@@ -338,27 +344,28 @@ static const char* enq_emit_launch(const EmitArgs& ea_in, hipStream_t st, uint64
 
 static bool enq_emit_blocks(cyc_ctx* c, hipStream_t st, uint64_t* out_in, uint64_t* out_eg, uint8_t* d_status) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
   if (pb.blocks.empty()) return false;
   if (!pb.K || !d_status) return true;  // nothing to write (the status plane of blocks is their slabs)
   BlockArgs ba{};
   ba.n_blk = uint32_t(pb.blocks.size());
   ba.K = pb.K;
-  ba.AS = c->blk_wa_max;
-  ba.blk = c->blk.as<uint4>();
-  ba.boff = c->blk_off.as<uint64_t>();
+  ba.AS = prep.blk_wa_max;
+  ba.blk = prep.blk.as<uint4>();
+  ba.boff = prep.blk_off.as<uint64_t>();
   for (int pl = 0; pl < 2; pl++) {
-    ba.pod_id[pl] = c->dir[pl].pod_id.as<uint32_t>();
-    ba.class_of[pl] = c->dir[pl].class_of.as<uint32_t>();
-    ba.A[pl] = c->dir[pl].A.as<uint64_t>();
+    ba.pod_id[pl] = prep.dir[pl].pod_id.as<uint32_t>();
+    ba.class_of[pl] = prep.dir[pl].class_of.as<uint32_t>();
+    ba.A[pl] = prep.dir[pl].A.as<uint64_t>();
   }
-  ba.st_src = c->slot_status.as<uint8_t>();
+  ba.st_src = prep.slot_status.as<uint8_t>();
   ba.out[0] = out_in;
   ba.out[1] = out_eg;
   ba.st_out = d_status;
   // a block's slab words split over workgroups of ~16 words per thread (one workgroup per block
   // left a few large blocks on a few CUs); small blocks' extra workgroups exit at once
-  const unsigned bs = c->blk_np_max * 2 > 128 ? 256 : 128;
-  const uint64_t most = 2ull * c->blk_np_max * pb.K * ((c->blk_np_max + 63) / 64);  // largest slab, both planes
+  const unsigned bs = prep.blk_np_max * 2 > 128 ? 256 : 128;
+  const uint64_t most = 2ull * prep.blk_np_max * pb.K * ((prep.blk_np_max + 63) / 64);  // largest slab, both planes
   ba.split = uint32_t(std::min<uint64_t>(64, std::max<uint64_t>(1, most / (uint64_t(bs) * 16))));
   k_emit_blocks<<<ba.n_blk * ba.split, bs, 0, st>>>(ba);
   return true;
@@ -370,49 +377,52 @@ static bool enq_emit_blocks(cyc_ctx* c, hipStream_t st, uint64_t* out_in, uint64
 static bool enq_emit(cyc_ctx* c, hipStream_t st, uint64_t* out_in, uint64_t* out_eg, uint8_t* d_status, bool inplace = false,
                      int part = 0) {
   Problem& pb = c->pb;
-  if (part != 1) c->ip_rng_clean = false;  // (set again below when this emit resets the spans for the next run)
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
+  if (part != 1) prep.ip_rng_clean = false;  // (set again below when this emit resets the spans for the next run)
   const uint32_t K = pb.K;
-  const uint64_t rw[2] = {uint64_t(K) * c->win_wa, uint64_t(K) * pb.W};  // words per plane row
+  const uint64_t rw[2] = {uint64_t(K) * rp.win_wa, uint64_t(K) * pb.W};  // words per plane row
   uint32_t nr[2];
-  for (int d = 0; d < 2; d++) nr[d] = rw[d] ? uint32_t(c->rh[d] - c->rl[d]) : 0u;
+  for (int d = 0; d < 2; d++) nr[d] = rw[d] ? uint32_t(rp.rh[d] - rp.rl[d]) : 0u;
   if (part != 2) {
-    c->emit_kernel.clear();
-    c->emit_launches = 0;
+    c->run.last.emit_kernel.clear();
+    c->run.last.emit_launches = 0;
   }
   if (!pb.blocks.empty()) {
     const bool r = enq_emit_blocks(c, st, out_in, out_eg, d_status);
-    if (r && pb.K && d_status) c->emit_kernel = "k_emit_blocks", c->emit_launches = 1;
+    if (r && pb.K && d_status) c->run.last.emit_kernel = "k_emit_blocks", c->run.last.emit_launches = 1;
     return r;
   }
   if (!nr[0] && !nr[1]) return false;
   EmitArgs ea{};
-  ea.st_src = c->slot_status.as<uint8_t>();
+  ea.st_src = prep.slot_status.as<uint8_t>();
   ea.st_dst = d_status;
   ea.st_bytes = d_status ? uint64_t(pb.P) * K : 0;
-  ea.reset = c->ip_rng.as<uint32_t>();
+  ea.reset = prep.ip_rng.as<uint32_t>();
   ea.reset_n = pb.may_err ? 0u : uint64_t(pb.peers.size()) * 4;  // (k_ip_rows with panics keeps no spans)
-  if (part != 1) c->ip_rng_clean = ea.reset_n != 0;
+  if (part != 1) prep.ip_rng_clean = ea.reset_n != 0;
   for (uint32_t pl = 0; pl < 2; pl++) {
-    ea.row_lo[pl] = uint32_t(c->rl[pl]);
-    ea.order[pl] = c->order[pl].as<uint2>();
-    ea.class_of[pl] = c->dir[pl].class_of.as<uint32_t>();
-    ea.A[pl] = c->dir[pl].A.as<uint64_t>();
-    ea.arow[pl] = inplace ? c->arow[pl].as<uint32_t>() : nullptr;
+    ea.row_lo[pl] = uint32_t(rp.rl[pl]);
+    ea.order[pl] = rp.order[pl].as<uint2>();
+    ea.class_of[pl] = prep.dir[pl].class_of.as<uint32_t>();
+    ea.A[pl] = prep.dir[pl].A.as<uint64_t>();
+    ea.arow[pl] = inplace ? rp.arow[pl].as<uint32_t>() : nullptr;
   }
   ea.out[0] = out_in;
   ea.out[1] = out_eg;
   ea.pl_words[0] = rw[0];
   ea.pl_words[1] = rw[1];
   auto note = [&](const char* k) {  // what cyc_last_emit reports
-    if (c->emit_kernel.find(k) == std::string::npos) c->emit_kernel += (c->emit_kernel.empty() ? "" : " + ") + std::string(k);
-    c->emit_launches++;
+    std::string& names = c->run.last.emit_kernel;
+    if (names.find(k) == std::string::npos) names += (names.empty() ? "" : " + ") + std::string(k);
+    c->run.last.emit_launches++;
   };
   if (rw[0] == rw[1] && nr[0] == nr[1]) {  // target rows: both planes in one launch
     ea.row_words = rw[0];
     ea.interleave = c->route.emit_interleave ? 1u : 0u;
     ea.n_rows[0] = ea.n_rows[1] = nr[0];
     if (part) {  // row phases (target rows over the whole table: both planes split at the same row)
-      const uint32_t n1 = c->phase_n1[0];
+      const uint32_t n1 = rp.phase_n1[0];
       ea.n_rows[0] = ea.n_rows[1] = part == 1 ? n1 : nr[0] - n1;
       for (int pl = 0; pl < 2; pl++) ea.order[pl] += part == 1 ? 0u : n1;
       if (part == 1) ea.reset_n = 0;
@@ -466,8 +476,10 @@ struct FrontLaunches {
 // phases (row phases, Route::phase_split): the class rows as two launches, phase 1's emit between them.
 static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_in, uint64_t* out_eg, bool phases) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
   const uint32_t P = pb.P, K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
-  const uint32_t M = uint32_t(pb.pms.size()), E = c->dir[1].n, EW = (E + 63) / 64;
+  const uint32_t M = uint32_t(pb.pms.size()), E = prep.dir[1].n, EW = (E + 63) / 64;
   FrontLaunches fl{};
   fl.phases = phases;
   bool& fits = fl.fits;
@@ -481,147 +493,147 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
   FrontRows &fd = fl.fd, &fe = fl.fe;
   const bool ido = route.ido;
   // A: IP word spans | port table | slot words | selectors
-  fa.fill_p = c->ip_rng.as<uint32_t>();
+  fa.fill_p = prep.ip_rng.as<uint32_t>();
   // the word spans and chunk masks of the IP rows and of PM builds' sparse pod rows (cnz needs no reset)
-  fa.fill_n = (c->Ri || c->Rr || (!ido && c->Rp)) ? pb.peers.size() * 4 : 0;
+  fa.fill_n = (rp.Ri || rp.Rr || (!ido && rp.Rp)) ? pb.peers.size() * 4 : 0;
   fa.nb[0] = blocks((fa.fill_n + 255) / 256);
   fa.M = M;
   fa.D = D;
   fa.P = P;
   fa.K = K;
   fa.W = W;
-  fa.pms = c->pms.as<DPortM>();
-  fa.pents = c->pents.as<DPortEntry>();
-  fa.descs = c->descs.as<DDesc>();
-  fa.portok = c->portok.as<uint8_t>();
+  fa.pms = prep.pms.as<DPortM>();
+  fa.pents = prep.pents.as<DPortEntry>();
+  fa.descs = prep.descs.as<DDesc>();
+  fa.portok = prep.portok.as<uint8_t>();
   fa.nb[1] = (M && pb.descs.size()) ? blocks((uint64_t(M) * D + 255) / 256) : 0u;
-  fa.slot_desc = c->slot_desc.as<int32_t>();
-  fa.slot_status = c->slot_status.as<uint8_t>();
-  fa.VALID = c->VALID.as<uint64_t>();
-  fa.DESCW = c->DESCW.as<int32_t>();
-  fa.DM = c->DM.as<uint64_t>();
+  fa.slot_desc = prep.slot_desc.as<int32_t>();
+  fa.slot_status = prep.slot_status.as<uint8_t>();
+  fa.VALID = prep.VALID.as<uint64_t>();
+  fa.DESCW = prep.DESCW.as<int32_t>();
+  fa.DM = prep.DM.as<uint64_t>();
   fa.nb[2] = route.slot_words ? blocks((uint64_t(K) * W + 3) / 4) : 0u;
-  fa.S = c->n_sel;
+  fa.S = rp.n_sel;
   fa.L = pb.L;
-  fa.sel_off = c->sel_off.as<uint32_t>();
-  fa.dreqs = c->dreqs.as<DReq>();
-  fa.req_vals = c->req_vals.as<uint32_t>();
-  fa.LVT = c->lvt.as<uint32_t>();
-  fa.selres = c->selres.as<uint8_t>();
-  fa.sel_list = c->sel_list.as<uint32_t>();
-  fa.nb[3] = uint64_t(c->n_sel) * pb.L && !route.lazy_sel ? blocks(uint64_t(c->n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))) : 0u;
+  fa.sel_off = prep.sel_off.as<uint32_t>();
+  fa.dreqs = prep.dreqs.as<DReq>();
+  fa.req_vals = prep.req_vals.as<uint32_t>();
+  fa.LVT = prep.lvt.as<uint32_t>();
+  fa.selres = prep.selres.as<uint8_t>();
+  fa.sel_list = rp.sel_list.as<uint32_t>();
+  fa.nb[3] = uint64_t(rp.n_sel) * pb.L && !route.lazy_sel ? blocks(uint64_t(rp.n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))) : 0u;
   // B: IP rows | pod-peer identity sets (both directions' adjacent sub-lists) | membership x 2
   // Segments x = 0, 1 of the IP rows and per-pod pod rows: the directions' sub-lists with their own
   // word windows (source shards), or both directions in segment 0 (one window)
   const bool one_win = route.one_window;
   fb.P = P;
   fb.W = W;
-  fb.ip_ex = c->ip_ex.as<DCidr>();
-  fb.pod_ip = c->pod_ip.as<DIP>();
-  fb.words = c->ip_words.as<DWordIP>();
-  fb.PM = c->PM.as<uint64_t>();
-  fb.rng = c->ip_rng.as<uint32_t>();
+  fb.ip_ex = rp.ip_ex.as<DCidr>();
+  fb.pod_ip = prep.pod_ip.as<DIP>();
+  fb.words = prep.ip_words.as<DWordIP>();
+  fb.PM = prep.PM.as<uint64_t>();
+  fb.rng = prep.ip_rng.as<uint32_t>();
   fb.cnz = ip_cnz(c);
   fb.ip_grp = IP_GROUP;
-  fb.ipr_iv = c->ipr_iv.as<uint2>();
-  fb.ipsort = c->ipsort.as<uint32_t>();
-  fb.ipv_iv = c->ipv_iv.as<uint2>();
-  fb.ip_ilist = c->ipi_list.as<uint32_t>();
+  fb.ipr_iv = rp.ipr_iv.as<uint2>();
+  fb.ipsort = prep.ipsort.as<uint32_t>();
+  fb.ipv_iv = rp.ipv_iv.as<uint2>();
+  fb.ip_ilist = rp.ipi_list.as<uint32_t>();
   for (int x = 0; x < 2; x++) {
     const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
-    const uint32_t i0 = c->ri_off[dlo];
-    fb.Ri[x] = one_win && x ? 0u : c->ri_off[dhi] - i0;
-    fb.tests[x] = c->ip_tests.as<DIPTest>() + i0;
-    peer_chunks(c, one_win ? 1 : x, fb.ic0[x], fb.inch[x]);
+    const uint32_t i0 = rp.ri_off[dlo];
+    fb.Ri[x] = one_win && x ? 0u : rp.ri_off[dhi] - i0;
+    fb.tests[x] = rp.ip_tests.as<DIPTest>() + i0;
+    peer_chunks(c->range, c->pb.W, one_win ? 1 : x, fb.ic0[x], fb.inch[x]);
     fb.nb[x] = fb.Ri[x] && fb.inch[x] ? blocks(ip_rows_blocks(fb.Ri[x], fb.inch[x], fb.ip_grp)) : 0u;
-    if (c->ip_items && fb.nb[x]) {  // the range plan's work items of this segment
-      fb.ip_items[x] = c->ipi_items.as<DIPItem>() + c->ipi_off[x];
-      fb.n_ip_items[x] = c->ipi_off[x + 1] - c->ipi_off[x];
+    if (rp.ip_items && fb.nb[x]) {  // the range plan's work items of this segment
+      fb.ip_items[x] = rp.ipi_items.as<DIPItem>() + rp.ipi_off[x];
+      fb.n_ip_items[x] = rp.ipi_off[x + 1] - rp.ipi_off[x];
       fb.nb[x] = blocks((uint64_t(fb.n_ip_items[x]) + 3) / 4);
     }
-    fb.Rr[x] = one_win && x ? 0u : c->rr_off[dhi] - c->rr_off[dlo];
-    fb.rtests[x] = c->ipr_tests.as<DIPRange>() + c->rr_off[dlo];
+    fb.Rr[x] = one_win && x ? 0u : rp.rr_off[dhi] - rp.rr_off[dlo];
+    fb.rtests[x] = rp.ipr_tests.as<DIPRange>() + rp.rr_off[dlo];
     fb.nb[9 + x] = fb.Rr[x] && fb.inch[x] ? blocks((uint64_t(fb.Rr[x]) + 3) / 4) : 0u;
-    fb.Rv[x] = one_win && x ? 0u : c->rv_off[dhi] - c->rv_off[dlo];
-    fb.vtests[x] = c->ipv_tests.as<DIPIv>() + c->rv_off[dlo];
+    fb.Rv[x] = one_win && x ? 0u : rp.rv_off[dhi] - rp.rv_off[dlo];
+    fb.vtests[x] = rp.ipv_tests.as<DIPIv>() + rp.rv_off[dlo];
     fb.nb[11 + x] = fb.Rv[x] && fb.inch[x] ? blocks((uint64_t(fb.Rv[x]) + 3) / 4) : 0u;
   }
   fb.E = E;
   fb.EW = EW;
   fb.L = pb.L;
-  fb.peers = c->peers.as<DPeer>();
-  fb.selres = c->selres.as<uint8_t>();
-  fb.id_ns = c->dir[1].id_ns.as<uint32_t>();
-  fb.id_nsls = c->id_nsls.as<uint32_t>();
-  fb.id_ls = c->dir[1].id_ls.as<uint32_t>();
+  fb.peers = prep.peers.as<DPeer>();
+  fb.selres = prep.selres.as<uint8_t>();
+  fb.id_ns = prep.dir[1].id_ns.as<uint32_t>();
+  fb.id_nsls = prep.id_nsls.as<uint32_t>();
+  fb.id_ls = prep.dir[1].id_ls.as<uint32_t>();
   fb.sv = sel_view(c);
-  fb.word_ns = c->ido_word_ns.as<uint2>();
+  fb.word_ns = rp.ido_word_ns.as<uint2>();
   for (int x = 0; x < 2; x++) {  // identity sets per direction: the ingress ones over the window's identity words
-    const uint32_t ux = c->rpu_off[x];
-    fb.Ru_[x] = c->rpu_off[x + 1] - ux;
-    fb.pod_peers_u_[x] = c->pod_peers_u.as<uint32_t>() + ux;
-    fb.idob_[x] = c->idob.as<uint64_t>() + uint64_t(ux) * EW;
-    fb.grp_ns_[x] = c->ido_grp_ns.as<uint2>() + c->ido_goff[x];
-    fb.pbrec_[x] = c->pb_rec.p && CYC_PB_REC ? c->pb_rec.as<uint4>() + 3 * uint64_t(ux) : nullptr;
-    fb.ew0[x] = x == 0 ? c->ido_ew0 : 0u;
-    fb.new_[x] = x == 0 ? c->ido_ew1 - c->ido_ew0 : EW;
+    const uint32_t ux = rp.rpu_off[x];
+    fb.Ru_[x] = rp.rpu_off[x + 1] - ux;
+    fb.pod_peers_u_[x] = rp.pod_peers_u.as<uint32_t>() + ux;
+    fb.idob_[x] = prep.idob.as<uint64_t>() + uint64_t(ux) * EW;
+    fb.grp_ns_[x] = rp.ido_grp_ns.as<uint2>() + rp.ido_goff[x];
+    fb.pbrec_[x] = rp.pb_rec.p && CYC_PB_REC ? rp.pb_rec.as<uint4>() + 3 * uint64_t(ux) : nullptr;
+    fb.ew0[x] = x == 0 ? rp.ido_ew0 : 0u;
+    fb.new_[x] = x == 0 ? rp.ido_ew1 - rp.ido_ew0 : EW;
     fb.nb[2 + x] = (fb.Ru_[x] && E && fb.new_[x]) ? blocks((uint64_t((fb.Ru_[x] + PB_GROUP - 1) / PB_GROUP) * fb.new_[x] + 3) / 4) : 0u;
   }
   if (!ido && !route.pod_sparse) {  // PM builds, few pod-peer words: full rows, a wave per (pod peer, word)
     fb.pod_direct = 1;
-    fb.pod_eid = c->dir[1].pod_id.as<uint32_t>();
+    fb.pod_eid = prep.dir[1].pod_id.as<uint32_t>();
     for (int x = 0; x < 2; x++) {
       const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
-      fb.Rp[x] = one_win && x ? 0u : c->rp_off[dhi] - c->rp_off[dlo];
-      fb.plist[x] = c->pod_peers.as<uint32_t>() + c->rp_off[dlo];
-      peer_window(c, one_win ? 1 : x, fb.pw0[x], fb.pnw[x]);
+      fb.Rp[x] = one_win && x ? 0u : rp.rp_off[dhi] - rp.rp_off[dlo];
+      fb.plist[x] = rp.pod_peers.as<uint32_t>() + rp.rp_off[dlo];
+      peer_window(c->range, c->pb.W, one_win ? 1 : x, fb.pw0[x], fb.pnw[x]);
       fb.nb[2 + x] = (fb.Rp[x] && E && fb.pnw[x]) ? blocks((pod_direct_waves(fb.Rp[x], fb.pnw[x]) + 3) / 4) : 0u;
     }
   } else if (!ido) {  // PM builds: sparse pod-peer rows in launch C (k_front_c)
     fb.nb[2] = fb.nb[3] = 0;
     fc.P = P;
     fc.W = W;
-    fc.req_post = c->req_post.as<uint4>();
-    fc.post_pods = c->post_pods.as<uint32_t>();
-    fc.peers = c->peers.as<DPeer>();
-    fc.pod_ns = c->pod_ns.as<uint32_t>();
-    fc.pod_nsls = c->pod_nsls.as<uint32_t>();
-    fc.pod_ls = c->pod_ls.as<uint32_t>();
-    fc.nsw = c->ns_words.as<DWordNS>();
+    fc.req_post = prep.req_post.as<uint4>();
+    fc.post_pods = prep.post_pods.as<uint32_t>();
+    fc.peers = prep.peers.as<DPeer>();
+    fc.pod_ns = prep.pod_ns.as<uint32_t>();
+    fc.pod_nsls = prep.pod_nsls.as<uint32_t>();
+    fc.pod_ls = prep.pod_ls.as<uint32_t>();
+    fc.nsw = prep.ns_words.as<DWordNS>();
     fc.sv = sel_view(c);
-    fc.PM = c->PM.as<uint64_t>();
-    fc.rng = c->ip_rng.as<uint32_t>();
+    fc.PM = prep.PM.as<uint64_t>();
+    fc.rng = prep.ip_rng.as<uint32_t>();
     fc.cnz = ip_cnz(c);
     // a wave per chunk over groups of 8 peers once that fills the chip (>= 64k peer chunks:
     // config #3u 2.6 vs 3.2 ms), else the 4 waves of a block share each chunk (config #2)
     uint64_t peer_chunks_all = 0;
     for (int x = 0; x < 2; x++) {
       const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
-      fc.Rp[x] = one_win && x ? 0u : c->scan_off[dhi] - c->scan_off[dlo];
-      fc.plist[x] = c->pp_scan.as<uint32_t>() + c->scan_off[dlo];
-      fc.plist_post[x] = c->pp_post.as<uint32_t>() + c->post_off[dlo];
-      peer_chunks(c, one_win ? 1 : x, fc.c0[x], fc.nch[x]);
+      fc.Rp[x] = one_win && x ? 0u : rp.scan_off[dhi] - rp.scan_off[dlo];
+      fc.plist[x] = rp.pp_scan.as<uint32_t>() + rp.scan_off[dlo];
+      fc.plist_post[x] = rp.pp_post.as<uint32_t>() + rp.post_off[dlo];
+      peer_chunks(c->range, c->pb.W, one_win ? 1 : x, fc.c0[x], fc.nch[x]);
       peer_chunks_all += uint64_t(fc.Rp[x]) * fc.nch[x];
     }
-    fc.pr_grp = c->pr_group > 0 ? uint32_t(c->pr_group) : (peer_chunks_all >= 65536 ? 8u : 1u);
+    fc.pr_grp = c->opt.pr_group > 0 ? uint32_t(c->opt.pr_group) : (peer_chunks_all >= 65536 ? 8u : 1u);
     for (int x = 0; x < 2; x++) {
       const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
       const uint64_t cb = (fc.nch[x] + 3) / 4;
       fc.nb[2 + x] = (fc.Rp[x] && E && cb) ? blocks((uint64_t(fc.Rp[x]) + fc.pr_grp - 1) / fc.pr_grp * cb) : 0u;
-      fc.nb[4 + x] = E && fc.nch[x] && !(one_win && x) ? c->post_off[dhi] - c->post_off[dlo] : 0u;  // a block per posting-built peer
+      fc.nb[4 + x] = E && fc.nch[x] && !(one_win && x) ? rp.post_off[dhi] - rp.post_off[dlo] : 0u;  // a block per posting-built peer
     }
   }
   size_t &lds = fl.lds, &lds_uni = fl.lds_uni, e_per[2] = {0, 0};
   uint32_t na_all[2];  // active identities per direction
   for (int d = 0; d < 2; d++) {
-    const uint32_t na = na_all[d] = c->dir[d].n ? c->n_act[d] : 0u;
+    const uint32_t na = na_all[d] = prep.dir[d].n ? rp.n_act[d] : 0u;
     fb.ma[d] = member_args(c, d);
     fc.ma[d] = fb.ma[d];
     if (phases) {  // the class election lists phase 2's classes apart (from the tail of reps[])
-      fc.ma[d].first_row = c->arow[d].as<uint32_t>();
+      fc.ma[d].first_row = rp.arow[d].as<uint32_t>();
       fc.ma[d].split = route.phase_split;
     }
-    fc.class_of[d] = c->dir[d].class_of.as<uint32_t>();
+    fc.class_of[d] = prep.dir[d].class_of.as<uint32_t>();
     fb.member_wave[d] = route.member_wave[d];
     fb.nb[4 + d] = na ? blocks(fb.member_wave[d] ? (uint64_t(na) + 3) / 4 : (uint64_t(na) + 255) / 256) : 0u;
     fc.nb[d] = na ? blocks((uint64_t(na) + 255) / 256) : 0u;
@@ -629,14 +641,14 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
     fd.ra[d] = row_args(c, d);  // its blocks empty the direction's hash table for the next run
     if (out_in && out_eg) {
       fd.ra[d].A = d == 0 ? out_in : out_eg;
-      fd.ra[d].arow = c->arow[d].as<uint32_t>();
+      fd.ra[d].arow = rp.arow[d].as<uint32_t>();
     }
     // (the class election keeps a launch of its own, C: electing inside the next launch's blocks put
     // the election chain on every block — IDO identity sets C + D 29 -> 45 us, PM class rows C + D
     // 79 -> 117 us on config #4: profiles/r04_elect_ab.txt)
     if (!ido) {  // PM builds: launch D (k_front_d_pm) is the class rows from flattened peer lists
       fd.nb[d] = pl_blocks(c, d);
-      if (d == 1 && c->uni_desc && c->pb.blocks.empty()) fd.ra[d].udesc = c->udesc.as<int32_t>();
+      if (d == 1 && prep.uni_desc && c->pb.blocks.empty()) fd.ra[d].udesc = prep.udesc.as<int32_t>();
       fd.ra[d].pod_sparse = route.pod_sparse;  // pod rows from pod_rows_sparse_blk (launch C)
       continue;
     }
@@ -644,7 +656,7 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
     fe.ra[d].ht_clear_words = 0;  // (launch D's identity sets empty it)
     fd.nb[d] = blocks((uint64_t(na) * ((fd.ra[d].NB + CI_G - 1) / CI_G) + 3) / 4);
     // egress with one descriptor per slot (udesc): only the block's slots' sets are staged
-    if (d == 1 && c->uni_desc) fe.ra[d].udesc = c->udesc.as<int32_t>();
+    if (d == 1 && prep.uni_desc) fe.ra[d].udesc = prep.udesc.as<int32_t>();
     e_per[d] = ido_rep_lds(d == 0 || fe.ra[d].udesc ? uint32_t(E_KC) : D, fd.ra[d].EW);
   }
   // launch E's representatives per block: the most of 16 / 8 that still leaves >= 3000 blocks
@@ -655,7 +667,7 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
   // (config #3 phased E per step, 8 per block against 16: 121.4 vs 141.8 us on one box, 122.8 vs 123.8
   // on another — profiles/r06_class_rpb_ab.txt)
   auto e_blocks = [&](int d, uint32_t rpb) { return ido_row_blocks(fe.ra[d].WA, K, E_KC, na_all[d], rpb); };
-  uint32_t e_want = uint32_t(c->class_rpb_opt);
+  uint32_t e_want = uint32_t(c->opt.class_rpb);
   if (!e_want) {
     e_want = 4;
     for (uint32_t cand : {16u, 8u}) {
@@ -681,21 +693,21 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
   const uint32_t nb_bits = bits ? blocks((uint64_t(M) + 255) / 256) : 0u;
   fb.M = M;
   fb.D = D;
-  fb.portok = c->portok.as<uint8_t>();
-  fb.portbits = c->portbits.as<uint32_t>();
+  fb.portok = prep.portok.as<uint8_t>();
+  fb.portbits = prep.portbits.as<uint32_t>();
   fb.nb[6] = nb_bits;
-  fe.ra[1].portbits = bits && fe.nb[1] ? c->portbits.as<uint32_t>() : nullptr;
+  fe.ra[1].portbits = bits && fe.nb[1] ? prep.portbits.as<uint32_t>() : nullptr;
   // Without a selector table to build (lazy selectors) launch A is dropped: its port table, slot
   // words and port bits (from the matchers directly) join launch B — their readers are the class
   // rows, launches D / E — and the IP rows' word spans were reset by the previous run's emit
   // (EmitArgs::reset; a memset when they were not).  Captured graphs keep launch A: a replay must not
   // depend on the step before it.
-  if (fa.nb[3] == 0 && !c->capturing) {
+  if (fa.nb[3] == 0 && !c->run.capturing) {
     fb.pre = fa;
     fb.bits_direct = 1;
     fb.nb[7] = fa.nb[1];
     fb.nb[8] = fa.nb[2];
-    if (fa.fill_n && !c->ip_rng_clean) fl.span_fill = fa.fill_p, fl.span_fill_bytes = fa.fill_n * 4;
+    if (fa.fill_n && !prep.ip_rng_clean) fl.span_fill = fa.fill_p, fl.span_fill_bytes = fa.fill_n * 4;
     fa.nb[0] = fa.nb[1] = fa.nb[2] = 0;
   }
   fl.ga = uint64_t(fa.nb[0]) + fa.nb[1] + fa.nb[2] + fa.nb[3];
@@ -708,7 +720,7 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
       fl.nd[phase][d] = fd.nb[d];
       fl.ne[phase][d] = fe.nb[d];
       if (!CYC_PHASE_GRID || !phase) continue;
-      const uint32_t nph = phase == 1 ? c->n_act_ph1[d] : na_all[d] - c->n_act_ph1[d];
+      const uint32_t nph = phase == 1 ? rp.n_act_ph1[d] : na_all[d] - rp.n_act_ph1[d];
       if (ido && fe.nb[d]) fl.ne[phase][d] = blocks(ido_row_blocks(fe.ra[d].WA, K, E_KC, nph, fe.ra[d].rpb));
       else if (!ido && fd.nb[d]) fl.nd[phase][d] = std::min(fd.nb[d], nph);
     }
@@ -771,13 +783,13 @@ static void launch_front(cyc_ctx* c, hipStream_t st, FrontLaunches& fl, const Fr
 static bool enq_fused_step(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status, const FrontEvents& ev,
                            bool* status_done) {
   const Route& route = c->route;
-  c->phase_used = 0;
+  c->run.last.phase_used = 0;
   if (!route.fused) return false;
   const bool ip = route.inplace && d_in && d_eg;
   const bool phases = route.phase_split != 0;
   FrontLaunches fl = build_front(c, route, ip ? d_in : nullptr, ip ? d_eg : nullptr, phases);
   if (!fl.fits) return false;
-  if (phases) c->phase_used = 2;
+  if (phases) c->run.last.phase_used = 2;
   launch_front(c, st, fl, ev, [&] { enq_emit(c, st, d_in, d_eg, d_status, ip, 1); });
   *status_done = enq_emit(c, st, d_in, d_eg, d_status, ip, phases ? 2 : 0);
   return true;
@@ -787,20 +799,22 @@ static bool enq_fused_step(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t*
 // rows, classes), [2] after the class rows, [3] after both emits.
 static void enqueue_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status) {
   Problem& pb = c->pb;
-  HIPCHK(hipEventRecord(c->ev[0], st));
+  Prepared& prep = c->prep;
+  RunState& run = c->run;
+  HIPCHK(hipEventRecord(run.ev[0], st));
   bool status_done = false;
-  if (!enq_fused_step(c, st, d_in, d_eg, d_status, FrontEvents{c->ev[1], c->ev[2], c->ev_p[0], c->ev_p[1]}, &status_done)) {
+  if (!enq_fused_step(c, st, d_in, d_eg, d_status, FrontEvents{run.ev[1], run.ev[2], run.ev_p[0], run.ev_p[1]}, &status_done)) {
     enq_common(c, st);
     for (int d = 0; d < 2; d++) enq_peer_rows(c, d, st);
     for (int d = 0; d < 2; d++) enq_member(c, d, st);
-    HIPCHK(hipEventRecord(c->ev[1], st));
+    HIPCHK(hipEventRecord(run.ev[1], st));
     for (int d = 0; d < 2; d++) enq_class_rows(c, d, st);
-    HIPCHK(hipEventRecord(c->ev[2], st));
+    HIPCHK(hipEventRecord(run.ev[2], st));
     status_done = enq_emit(c, st, d_in, d_eg, d_status);
   }
-  HIPCHK(hipEventRecord(c->ev[3], st));
+  HIPCHK(hipEventRecord(run.ev[3], st));
   if (!status_done && d_status && uint64_t(pb.P) * pb.K)
-    HIPCHK(hipMemcpyAsync(d_status, c->slot_status.p, uint64_t(pb.P) * pb.K, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_status, prep.slot_status.p, uint64_t(pb.P) * pb.K, hipMemcpyDeviceToDevice, st));
 }
 
 // Graph capture / eager DAG: the fused front on st when it applies; else the two-branch DAG:
@@ -810,126 +824,128 @@ static void enqueue_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_
 static void capture_pipeline(cyc_ctx* c, hipStream_t st, hipStream_t st2, hipStream_t st3, uint64_t* d_in, uint64_t* d_eg,
                              uint8_t* d_status) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
   bool status_done = false;
   if (enq_fused_step(c, st, d_in, d_eg, d_status, FrontEvents{}, &status_done)) {
     if (status_done) return;
   } else {
-    HIPCHK(hipEventRecord(c->fork_ev, st));
-    HIPCHK(hipStreamWaitEvent(st3, c->fork_ev, 0));
+    HIPCHK(hipEventRecord(c->run.fork_ev, st));
+    HIPCHK(hipStreamWaitEvent(st3, c->run.fork_ev, 0));
     enq_common(c, st3, COMMON_FILL | COMMON_PORTS);
     enq_peer_rows(c, 2, st3, PEERS_IP);  // both directions' IP rows in one launch
-    HIPCHK(hipEventRecord(c->ports_ev, st3));
+    HIPCHK(hipEventRecord(c->run.ports_ev, st3));
     enq_common(c, st, COMMON_SELECTORS);
-    HIPCHK(hipEventRecord(c->sel_ev, st));
-    HIPCHK(hipStreamWaitEvent(st2, c->sel_ev, 0));
+    HIPCHK(hipEventRecord(c->run.sel_ev, st));
+    HIPCHK(hipStreamWaitEvent(st2, c->run.sel_ev, 0));
     for (int d = 1; d >= 0; d--) {
       hipStream_t s = d ? st2 : st;
       enq_peer_rows(c, d, s, PEERS_POD);
       enq_member(c, d, s);
-      HIPCHK(hipStreamWaitEvent(s, c->ports_ev, 0));
+      HIPCHK(hipStreamWaitEvent(s, c->run.ports_ev, 0));
       enq_class_rows(c, d, s);
     }
-    HIPCHK(hipEventRecord(c->join_ev, st2));
-    HIPCHK(hipStreamWaitEvent(st, c->join_ev, 0));
+    HIPCHK(hipEventRecord(c->run.join_ev, st2));
+    HIPCHK(hipStreamWaitEvent(st, c->run.join_ev, 0));
     // the emit also writes the status plane; the copy node below only ends steps without rows
     if (enq_emit(c, st, d_in, d_eg, d_status)) return;
   }
   // The step always ends with the status-plane copy (into a sink buffer when the caller passed no
   // status pointer), so every captured graph has the same shape: one node after the join.
   const uint64_t nst = uint64_t(pb.P) * pb.K;
-  uint8_t* dst = d_status && nst ? d_status : c->status_sink.as<uint8_t>();  // sink: >= 16 B (prepare_device)
-  HIPCHK(hipMemcpyAsync(dst, c->slot_status.p, std::max<uint64_t>(nst, 1), hipMemcpyDeviceToDevice, st));
+  uint8_t* dst = d_status && nst ? d_status : prep.status_sink.as<uint8_t>();  // sink: >= 16 B (prepare_device)
+  HIPCHK(hipMemcpyAsync(dst, prep.slot_status.p, std::max<uint64_t>(nst, 1), hipMemcpyDeviceToDevice, st));
 }
 
 // Destroy the retired execs whose last launch has completed (all of them when `wait`).
 static void reap_graphs(cyc_ctx* c, bool wait) {
   size_t keep = 0;
-  for (size_t i = 0; i < c->retired.size(); i++) {
-    cyc_ctx::Retired& r = c->retired[i];
+  for (size_t i = 0; i < c->run.retired.size(); i++) {
+    RunState::Retired& r = c->run.retired[i];
     if (r.done && wait) (void)hipEventSynchronize(r.done);
     const bool done = !r.done || wait || hipEventQuery(r.done) != hipErrorNotReady;
     if (!done) {
-      c->retired[keep++] = r;
+      c->run.retired[keep++] = r;
       continue;
     }
     (void)hipGraphExecDestroy(r.exec);
     if (r.graph) (void)hipGraphDestroy(r.graph);
     if (r.done) (void)hipEventDestroy(r.done);
   }
-  c->retired.resize(keep);
+  c->run.retired.resize(keep);
 }
 
 static void drop_graph(cyc_ctx* c) {
-  if (c->graph_exec) c->retired.push_back({c->graph_exec, c->graph, c->graph_done});
-  c->graph_exec = nullptr;
-  c->graph = nullptr;
-  c->graph_done = nullptr;
+  if (c->run.graph_exec) c->run.retired.push_back({c->run.graph_exec, c->run.graph, c->run.graph_done});
+  c->run.graph_exec = nullptr;
+  c->run.graph = nullptr;
+  c->run.graph_done = nullptr;
   reap_graphs(c, false);
 }
 
 static void ensure_cap_streams(cyc_ctx* c) {
-  if (c->cap_stream) return;
-  HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&c->cap_stream2, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&c->cap_stream3, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&c->sel_ev, EV_SYNC));
-  HIPCHK(hipEventCreateWithFlags(&c->ports_ev, EV_SYNC));
-  HIPCHK(hipEventCreateWithFlags(&c->fork_ev, EV_SYNC));
-  HIPCHK(hipEventCreateWithFlags(&c->join_ev, EV_SYNC));
+  if (c->run.cap_stream) return;
+  HIPCHK(hipStreamCreateWithFlags(&c->run.cap_stream, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&c->run.cap_stream2, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&c->run.cap_stream3, hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(&c->run.sel_ev, EV_SYNC));
+  HIPCHK(hipEventCreateWithFlags(&c->run.ports_ev, EV_SYNC));
+  HIPCHK(hipEventCreateWithFlags(&c->run.fork_ev, EV_SYNC));
+  HIPCHK(hipEventCreateWithFlags(&c->run.join_ev, EV_SYNC));
 }
 
 // Batched blocks: each block's status, as its stand-alone run would end — the job expansion's
 // panic, else its first panicking job (its own job order), else its table build's duplicate key —
-// into c->blk_rc / c->blk_msg.  Synchronises only when the inputs can panic.
+// into c->run.last.blk_rc / c->run.last.blk_msg.  Synchronises only when the inputs can panic.
 static int blocks_status(cyc_ctx* c, hipStream_t st) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
   const size_t nb = pb.blocks.size();
-  c->blk_rc.assign(nb, CYC_OK);
-  c->blk_msg.assign(nb, "");
+  c->run.last.blk_rc.assign(nb, CYC_OK);
+  c->run.last.blk_msg.assign(nb, "");
   std::vector<unsigned long long> first(nb, ~0ull);
   if (pb.may_err && pb.P && pb.K) {
-    HIPCHK(hipMemsetAsync(c->first_blk.p, 0xFF, nb * 8, st));
+    HIPCHK(hipMemsetAsync(prep.first_blk.p, 0xFF, nb * 8, st));
     BlockErrArgs e{};
     e.n_blk = uint32_t(nb);
     e.P = pb.P;
     e.K = pb.K;
-    e.AS = c->blk_wa_max;
-    e.blk = c->blk.as<uint4>();
+    e.AS = prep.blk_wa_max;
+    e.blk = prep.blk.as<uint4>();
     e.pod_blk = nullptr;
-    e.slot_idx = c->slot_idx.as<uint32_t>();
-    e.slot_status = c->slot_status.as<uint8_t>();
-    e.pod_iid = c->dir[0].pod_id.as<uint32_t>();
-    e.pod_eid = c->dir[1].pod_id.as<uint32_t>();
-    e.class_in = c->dir[0].class_of.as<uint32_t>();
-    e.class_eg = c->dir[1].class_of.as<uint32_t>();
-    e.err_in = c->dir[0].err.as<uint8_t>();
-    e.err_eg = c->dir[1].err.as<uint8_t>();
-    e.AE_in = c->dir[0].AE.as<uint64_t>();
-    e.AE_eg = c->dir[1].AE.as<uint64_t>();
-    e.first = c->first_blk.as<unsigned long long>();
-    e.dchunks = (c->blk_np_max + 255) / 256;
+    e.slot_idx = prep.slot_idx.as<uint32_t>();
+    e.slot_status = prep.slot_status.as<uint8_t>();
+    e.pod_iid = prep.dir[0].pod_id.as<uint32_t>();
+    e.pod_eid = prep.dir[1].pod_id.as<uint32_t>();
+    e.class_in = prep.dir[0].class_of.as<uint32_t>();
+    e.class_eg = prep.dir[1].class_of.as<uint32_t>();
+    e.err_in = prep.dir[0].err.as<uint8_t>();
+    e.err_eg = prep.dir[1].err.as<uint8_t>();
+    e.AE_in = prep.dir[0].AE.as<uint64_t>();
+    e.AE_eg = prep.dir[1].AE.as<uint64_t>();
+    e.first = prep.first_blk.as<unsigned long long>();
+    e.dchunks = (prep.blk_np_max + 255) / 256;
     DevBuf pod_blk;
     upload(pod_blk, pb.pod_blk);
     e.pod_blk = pod_blk.as<uint32_t>();
-    if (c->dir[0].n && c->dir[1].n)
+    if (prep.dir[0].n && prep.dir[1].n)
       k_first_error_blocks<<<grid1(uint64_t(pb.P) * e.dchunks, 1), 256, 0, st>>>(e);
-    HIPCHK(hipMemcpyAsync(first.data(), c->first_blk.p, nb * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(first.data(), prep.first_blk.p, nb * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
   const std::string saved = c->err;
   for (size_t b = 0; b < nb; b++) {
     const ProbeBlock& x = pb.blocks[b];
     if (pb.blk_expand_panic[b]) {
-      c->blk_rc[b] = CYC_ERR_PANIC_RUNTIME;
-      c->blk_msg[b] = "runtime error: index out of range [0] with length 0";
+      c->run.last.blk_rc[b] = CYC_ERR_PANIC_RUNTIME;
+      c->run.last.blk_msg[b] = "runtime error: index out of range [0] with length 0";
     } else if (first[b] != ~0ull) {
       const uint32_t np = x.p1 - x.p0, idx = uint32_t(first[b] % 65536);
       const uint64_t rest = first[b] / 65536;
-      c->blk_rc[b] = describe_panic(c, x.p0 + uint32_t(rest / np), x.p0 + uint32_t(rest % np), x.cfg, idx);
-      c->blk_msg[b] = c->err;
+      c->run.last.blk_rc[b] = describe_panic(c, x.p0 + uint32_t(rest / np), x.p0 + uint32_t(rest % np), x.cfg, idx);
+      c->run.last.blk_msg[b] = c->err;
     } else if (!pb.blk_dup_msg[b].empty()) {
-      c->blk_rc[b] = CYC_ERR_DUPLICATE_KEY;
-      c->blk_msg[b] = pb.blk_dup_msg[b];
+      c->run.last.blk_rc[b] = CYC_ERR_DUPLICATE_KEY;
+      c->run.last.blk_msg[b] = pb.blk_dup_msg[b];
     }
   }
   c->err = saved;
@@ -942,64 +958,66 @@ static int blocks_status(cyc_ctx* c, hipStream_t st) {
 static int run_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status, int64_t lo,
                         int64_t hi, bool allow_capture = true, bool src = false) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
   const uint32_t P = pb.P, K = pb.K, W = pb.W;
   if (lo < 0 || hi > int64_t(P) || lo > hi) return fail(c, CYC_ERR_ARG, "row range out of bounds");
   if (src && (lo % 64 || (hi % 64 && hi != int64_t(P))))
     return fail(c, CYC_ERR_ARG, "source rows: row_lo must be a multiple of 64, row_hi too unless it is the pod count");
-  if (c->order_lo != lo || c->order_hi != hi || c->order_src != src) drop_graph(c);  // range plan buffers are re-made
+  if (!rp.is(lo, hi, src)) drop_graph(c);  // range plan buffers are re-made
   ensure_range(c, lo, hi, src);
   const Route& route = c->route;
-  if (!c->plvt_ready && route.fused && route.pod_sparse) {
+  if (!prep.plvt_ready && route.fused && route.pod_sparse) {
     drop_graph(c);  // a graph captured without the per-pod table would keep the slower gathers
     ensure_plvt(c, st);
   }
   const bool dag = route.launch == 2 || !allow_capture;  // (of the runs that are not eager)
   if (route.runs_eager) {
     enqueue_pipeline(c, st, d_in, d_eg, d_status);
-    c->timed = true;
-    c->timed_graph = false;
+    c->run.last.timed = true;
+    c->run.last.timed_graph = false;
   } else if (dag) {
     // the graph's DAG, enqueued directly: the caller's stream forks to two internal streams and
     // joins them back before the emit (events), without hipGraphLaunch's per-replay latency
     ensure_cap_streams(c);
-    if (c->step_events) HIPCHK(hipEventRecord(c->ev[0], st));
-    capture_pipeline(c, st, c->cap_stream2, c->cap_stream3, d_in, d_eg, d_status);
-    if (c->step_events) HIPCHK(hipEventRecord(c->ev[3], st));
-    c->timed = c->step_events != 0;
-    c->timed_graph = true;
+    if (c->opt.step_events) HIPCHK(hipEventRecord(c->run.ev[0], st));
+    capture_pipeline(c, st, c->run.cap_stream2, c->run.cap_stream3, d_in, d_eg, d_status);
+    if (c->opt.step_events) HIPCHK(hipEventRecord(c->run.ev[3], st));
+    c->run.last.timed = c->opt.step_events != 0;
+    c->run.last.timed_graph = true;
   } else {
     // The whole pipeline as one hipGraph (captured once per output buffers / row range):
     // removes the host launch cost of ~16 launches per run (dominant on small problems).
     const void* key[6] = {d_in, d_eg, d_status, reinterpret_cast<void*>(lo), reinterpret_cast<void*>(hi),
                           reinterpret_cast<void*>(intptr_t(src))};
-    if (!c->graph_exec || memcmp(key, c->graph_key, sizeof(key)) != 0) {
+    if (!c->run.graph_exec || memcmp(key, c->run.graph_key, sizeof(key)) != 0) {
       drop_graph(c);
       ensure_cap_streams(c);
       hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-      c->capturing = true;
+      HIPCHK(hipStreamBeginCapture(c->run.cap_stream, hipStreamCaptureModeThreadLocal));
+      c->run.capturing = true;
       try {
-        capture_pipeline(c, c->cap_stream, c->cap_stream2, c->cap_stream3, d_in, d_eg, d_status);
+        capture_pipeline(c, c->run.cap_stream, c->run.cap_stream2, c->run.cap_stream3, d_in, d_eg, d_status);
       } catch (...) {
-        c->capturing = false;
+        c->run.capturing = false;
         throw;
       }
-      c->capturing = false;
-      HIPCHK(hipStreamEndCapture(c->cap_stream, &g));
-      c->graph = g;  // destroyed with the exec (drop_graph / reap_graphs)
-      HIPCHK(hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0));
-      HIPCHK(hipEventCreateWithFlags(&c->graph_done, EV_SYNC));
-      memcpy(c->graph_key, key, sizeof(key));
+      c->run.capturing = false;
+      HIPCHK(hipStreamEndCapture(c->run.cap_stream, &g));
+      c->run.graph = g;  // destroyed with the exec (drop_graph / reap_graphs)
+      HIPCHK(hipGraphInstantiate(&c->run.graph_exec, g, nullptr, nullptr, 0));
+      HIPCHK(hipEventCreateWithFlags(&c->run.graph_done, EV_SYNC));
+      memcpy(c->run.graph_key, key, sizeof(key));
     }
-    if (c->step_events) HIPCHK(hipEventRecord(c->ev[0], st));
-    HIPCHK(hipGraphLaunch(c->graph_exec, st));
-    HIPCHK(hipEventRecord(c->graph_done, st));  // the exec may be retired once this completes
-    if (c->step_events) HIPCHK(hipEventRecord(c->ev[3], st));
-    c->timed = c->step_events != 0;
-    c->timed_graph = true;
+    if (c->opt.step_events) HIPCHK(hipEventRecord(c->run.ev[0], st));
+    HIPCHK(hipGraphLaunch(c->run.graph_exec, st));
+    HIPCHK(hipEventRecord(c->run.graph_done, st));  // the exec may be retired once this completes
+    if (c->opt.step_events) HIPCHK(hipEventRecord(c->run.ev[3], st));
+    c->run.last.timed = c->opt.step_events != 0;
+    c->run.last.timed_graph = true;
   }
-  c->ran = true;
-  c->last_stream = st;  // cyc_last_classes waits for this stream only
+  c->run.last.ran = true;
+  c->run.last.stream = st;  // cyc_last_classes waits for this stream only
 
   if (!pb.blocks.empty()) return blocks_status(c, st);
 
@@ -1010,7 +1028,7 @@ static int run_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_
   if (pb.may_err) {
     if (P >= (1u << 24) || K > 65536)  // k_first_error's job-order key: (s*P + d)*65536 + idx < 2^64
       throw Panic{CYC_ERR_ARG, "inputs that can panic are limited to 2^24 pods and 65536 job slots"};
-    HIPCHK(hipMemsetAsync(c->first_err.p, 0xFF, uint64_t(pb.n_cfg) * 8, st));
+    HIPCHK(hipMemsetAsync(prep.first_err.p, 0xFF, uint64_t(pb.n_cfg) * 8, st));
     ErrArgs e{};
     e.P = P;
     e.K = K;
@@ -1019,23 +1037,23 @@ static int run_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_
     e.row_lo = uint32_t(lo);
     e.row_hi = uint32_t(hi);
     e.src = src ? 1u : 0u;
-    e.w0 = c->win_w0;
-    e.WA = c->win_wa;
-    e.slot_status = c->slot_status.as<uint8_t>();
-    e.slot_cfg = c->slot_cfg.as<uint32_t>();
-    e.slot_idx = c->slot_idx.as<uint32_t>();
-    e.pod_iid = c->dir[0].pod_id.as<uint32_t>();
-    e.pod_eid = c->dir[1].pod_id.as<uint32_t>();
-    e.class_in = c->dir[0].class_of.as<uint32_t>();
-    e.class_eg = c->dir[1].class_of.as<uint32_t>();
-    e.err_in = c->dir[0].err.as<uint8_t>();
-    e.err_eg = c->dir[1].err.as<uint8_t>();
-    e.AE_in = c->dir[0].n ? c->dir[0].AE.as<uint64_t>() : nullptr;
-    e.AE_eg = c->dir[1].n ? c->dir[1].AE.as<uint64_t>() : nullptr;
-    e.first = c->first_err.as<unsigned long long>();
+    e.w0 = rp.win_w0;
+    e.WA = rp.win_wa;
+    e.slot_status = prep.slot_status.as<uint8_t>();
+    e.slot_cfg = prep.slot_cfg.as<uint32_t>();
+    e.slot_idx = prep.slot_idx.as<uint32_t>();
+    e.pod_iid = prep.dir[0].pod_id.as<uint32_t>();
+    e.pod_eid = prep.dir[1].pod_id.as<uint32_t>();
+    e.class_in = prep.dir[0].class_of.as<uint32_t>();
+    e.class_eg = prep.dir[1].class_of.as<uint32_t>();
+    e.err_in = prep.dir[0].err.as<uint8_t>();
+    e.err_eg = prep.dir[1].err.as<uint8_t>();
+    e.AE_in = prep.dir[0].n ? prep.dir[0].AE.as<uint64_t>() : nullptr;
+    e.AE_eg = prep.dir[1].n ? prep.dir[1].AE.as<uint64_t>() : nullptr;
+    e.first = prep.first_err.as<unsigned long long>();
     if (P && K) k_first_error<<<grid1(uint64_t((P + 255) / 256) * P, 1), 256, 0, st>>>(e);
     std::vector<unsigned long long> first(std::max<uint32_t>(pb.n_cfg, 1), ~0ull);
-    HIPCHK(hipMemcpyAsync(first.data(), c->first_err.p, uint64_t(pb.n_cfg) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(first.data(), prep.first_err.p, uint64_t(pb.n_cfg) * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (uint32_t cc = 0; cc < pb.n_cfg; cc++)
       if (first[cc] != ~0ull) {
@@ -1060,11 +1078,13 @@ static int run_pipeline(cyc_ctx* c, hipStream_t st, uint64_t* d_in, uint64_t* d_
 // replaying that single job's evaluation order over the compiled tables (error path only).
 int describe_panic(cyc_ctx* c, uint32_t s, uint32_t d, uint32_t cfg, uint32_t idx) {
   Problem& pb = c->pb;
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
   uint32_t k = 0;
   for (uint32_t kk = 0; kk < pb.K; kk++)
     if (pb.slot_cfg[kk] == cfg && pb.slot_idx[kk] == idx) k = kk;
   std::vector<uint8_t> selres(size_t(pb.S) * pb.L);
-  HIPCHK(hipMemcpy(selres.data(), c->selres.p, selres.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(selres.data(), prep.selres.p, selres.size(), hipMemcpyDeviceToHost));
   auto sel = [&](uint32_t sid, uint32_t ls) { return selres[size_t(sid) * pb.L + ls]; };
   auto ip_err = [&](const DPeer& pr, uint32_t q, std::string& msg) -> int {
     const DIPBlock& b = pb.ipbs[pr.ipb];
@@ -1104,16 +1124,16 @@ int describe_panic(cyc_ctx* c, uint32_t s, uint32_t d, uint32_t cfg, uint32_t id
         if (pr.kind == 0) break;
         int32_t de = pb.slot_desc[size_t(d) * pb.K + k];
         std::vector<uint8_t> ok(1);
-        HIPCHK(hipMemcpy(ok.data(), c->portok.as<uint8_t>() + size_t(pr.port) * std::max<size_t>(pb.descs.size(), 1) + de, 1,
+        HIPCHK(hipMemcpy(ok.data(), prep.portok.as<uint8_t>() + size_t(pr.port) * std::max<size_t>(pb.descs.size(), 1) + de, 1,
                          hipMemcpyDeviceToHost));
         if (pr.kind == 1) {
           if (ok[0]) break;
           continue;
         }
         uint64_t pm, er;
-        const size_t row = pr.kind == 3 && j < c->prow_host.size() ? c->prow_host[j] : j;  // IP peers share their IPBlock's row
-        HIPCHK(hipMemcpy(&pm, c->PM.as<uint64_t>() + row * pb.W + peer / 64, 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&er, c->ER.as<uint64_t>() + row * pb.W + peer / 64, 8, hipMemcpyDeviceToHost));
+        const size_t row = pr.kind == 3 && j < rp.prow_host.size() ? rp.prow_host[j] : j;  // IP peers share their IPBlock's row
+        HIPCHK(hipMemcpy(&pm, prep.PM.as<uint64_t>() + row * pb.W + peer / 64, 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&er, prep.ER.as<uint64_t>() + row * pb.W + peer / 64, 8, hipMemcpyDeviceToHost));
         if ((er >> (peer % 64)) & 1) {
           if (pr.kind == 2) return fail(c, CYC_ERR_PANIC_SELECTOR, "invalid operator");
           std::string msg;
@@ -1128,12 +1148,12 @@ int describe_panic(cyc_ctx* c, uint32_t s, uint32_t d, uint32_t cfg, uint32_t id
 }
 
 static void destroy_events(cyc_ctx* c) {
-  for (auto& e : c->ev)
+  for (auto& e : c->run.ev)
     if (e) {
       (void)hipEventDestroy(e);
       e = nullptr;
     }
-  for (auto& e : c->ev_p)
+  for (auto& e : c->run.ev_p)
     if (e) {
       (void)hipEventDestroy(e);
       e = nullptr;

@@ -6,15 +6,13 @@
 // Pod identities per direction, numbered by first appearance in pod order: egress (namespace, label
 // set), ingress (namespace, label set, every slot's job status and descriptor).  Hashed into an
 // open-addressing table whose entries hold their first pod; a probe compares the pods' fields.
-static void build_identities(cyc_ctx* c) {
-  Problem& pb = c->pb;
+static void build_identities(const Problem& pb, Prepared& prep) {
   const uint32_t K = pb.K;
   uint32_t cap = 2;
   while (cap < 2 * std::max<uint32_t>(pb.P, 1)) cap <<= 1;
   std::vector<uint32_t> slot_pod(cap), slot_id(cap);
   for (int d = 0; d < 2; d++) {
-    Identities& I = c->ids[d];
-    I = Identities{};
+    Identities& I = prep.ids[d];
     I.of_pod.resize(pb.P);
     const bool slots = d == 0 && K;  // the ingress identity includes the pod's job descriptors
     std::fill(slot_pod.begin(), slot_pod.end(), UINT32_MAX);
@@ -112,43 +110,38 @@ static PeerPlan plan_peers(const Problem& pb, const Identities& eg) {
   return pl;
 }
 
-static uint64_t ido_b_bytes(const cyc_ctx* c, int d) {
-  const uint64_t EW = (c->ids[1].ns.size() + 63) / 64, D = std::max<size_t>(c->pb.descs.size(), 1);
-  return uint64_t(c->ids[d].ns.size()) * (d == 0 ? c->pb.K : D) * EW * 8;
+static uint64_t ido_b_bytes(const Problem& pb, const Prepared& prep, int d) {
+  const uint64_t EW = (prep.ids[1].ns.size() + 63) / 64, D = std::max<size_t>(pb.descs.size(), 1);
+  return uint64_t(prep.ids[d].ns.size()) * (d == 0 ? pb.K : D) * EW * 8;
 }
 
-static uint64_t ido_lds_bytes(const cyc_ctx* c) {  // k_class_rows_ido: staged identity-set rows
-  const uint64_t EW = (c->ids[1].ns.size() + 63) / 64, D = std::max<size_t>(c->pb.descs.size(), 1);
-  return std::max<uint64_t>(std::min<uint64_t>(8, c->pb.K), D) * EW * 8;  // KC <= 8 slot rows or D
+static uint64_t ido_lds_bytes(const Problem& pb, const Prepared& prep) {  // k_class_rows_ido: staged identity-set rows
+  const uint64_t EW = (prep.ids[1].ns.size() + 63) / 64, D = std::max<size_t>(pb.descs.size(), 1);
+  return std::max<uint64_t>(std::min<uint64_t>(8, pb.K), D) * EW * 8;  // KC <= 8 slot rows or D
 }
 
-// The route's facts as the context holds them now: options, the prepared problem, the current range plan.
-static RouteIn route_in(const cyc_ctx* c) {
-  const Problem& pb = c->pb;
+// The route's facts: the options, the prepared problem, a range plan (RangePlan{}: no rows planned yet).
+static RouteIn route_in(const Options& opt, const Problem& pb, const Prepared& prep, const RangePlan& rp) {
   RouteIn in;
-  in.use_graphs = c->use_graphs, in.front_fused = c->front_fused, in.pod_words = c->pod_words, in.pod_rows = c->pod_rows;
-  in.member_wave = c->member_wave, in.pl_wave = c->pl_wave, in.sel_lazy = c->sel_lazy, in.pr_group = c->pr_group;
-  in.class_inplace = c->class_inplace, in.emit_interleave = c->emit_interleave, in.row_phases = c->row_phases;
+  in.opt = opt;
   in.P = pb.P, in.K = pb.K, in.W = pb.W, in.L = pb.L;
   in.n_desc = uint32_t(pb.descs.size()), in.n_pm = uint32_t(pb.pms.size());
   in.may_err = pb.may_err, in.blocks = !pb.blocks.empty();
-  in.dense_sel = c->dense_sel, in.uni_desc = c->uni_desc, in.n_sel = c->n_sel, in.max_runs = c->plan.max_runs;
-  in.ido_lds_bytes = ido_lds_bytes(c), in.ido_b_bytes = ido_b_bytes(c, 0) + ido_b_bytes(c, 1);
-  in.E = c->dir[1].n;
-  for (int d = 0; d < 2; d++) in.n_act[d] = c->n_act[d], in.act_targets[d] = c->act_targets[d], in.rows[d] = c->rh[d] - c->rl[d];
-  std::copy(c->rp_off, c->rp_off + 3, in.rp_off);
-  in.win_w0 = c->win_w0, in.win_wa = c->win_wa;
-  in.whole = c->rl[1] == 0 && c->rh[1] == int64_t(pb.P), in.src = c->order_src;
+  in.dense_sel = prep.dense_sel, in.uni_desc = prep.uni_desc, in.max_runs = prep.plan.max_runs;
+  in.ido_lds_bytes = ido_lds_bytes(pb, prep), in.ido_b_bytes = ido_b_bytes(pb, prep, 0) + ido_b_bytes(pb, prep, 1);
+  in.E = uint32_t(prep.ids[1].ns.size());
+  in.n_sel = rp.n_sel;
+  for (int d = 0; d < 2; d++) in.n_act[d] = rp.n_act[d], in.act_targets[d] = rp.act_targets[d], in.rows[d] = rp.rh[d] - rp.rl[d];
+  std::copy(rp.rp_off, rp.rp_off + 3, in.rp_off);
+  in.win_w0 = rp.win_w0, in.win_wa = rp.win_wa;
+  in.whole = rp.rl[1] == 0 && rp.rh[1] == int64_t(pb.P), in.src = rp.src;
   return in;
 }
-static void reroute(cyc_ctx* c) { c->route = resolve_route(route_in(c)); }
+static void reroute(cyc_ctx* c) { c->route = resolve_route(route_in(c->opt, c->pb, c->prep, c->range)); }
 
 // Batched blocks: per block (first pod, pods, first slot, slots) and its output slab offsets; per
 // identity its block and class-row window (its block's words).
-static void prepare_blocks_device(cyc_ctx* c) {
-  Problem& pb = c->pb;
-  c->blk_off_h.clear();
-  c->blk_wa_max = c->blk_np_max = 0;
+static void prepare_blocks_device(const Problem& pb, Prepared& prep) {
   if (pb.blocks.empty()) return;
   std::vector<uint32_t> cfg_k0(pb.n_cfg + 1, pb.K), cfg_nk(pb.n_cfg, 0);
   for (uint32_t k = pb.K; k-- > 0;) cfg_k0[pb.slot_cfg[k]] = k;
@@ -159,19 +152,19 @@ static void prepare_blocks_device(cyc_ctx* c) {
     const ProbeBlock& x = pb.blocks[b];
     const uint32_t np = x.p1 - x.p0, nk = cfg_nk[x.cfg];
     bl[b] = uint4{x.p0, np, cfg_k0[x.cfg], nk};
-    c->blk_off_h.push_back(words);
-    c->blk_off_h.push_back(bytes);
+    prep.blk_off_h.push_back(words);
+    prep.blk_off_h.push_back(bytes);
     words += uint64_t(np) * nk * ((np + 63) / 64);
     bytes += uint64_t(np) * nk;
-    c->blk_wa_max = std::max<uint32_t>(c->blk_wa_max, np ? (x.p1 + 63) / 64 - x.p0 / 64 : 0u);
-    c->blk_np_max = std::max(c->blk_np_max, np);
+    prep.blk_wa_max = std::max<uint32_t>(prep.blk_wa_max, np ? (x.p1 + 63) / 64 - x.p0 / 64 : 0u);
+    prep.blk_np_max = std::max(prep.blk_np_max, np);
   }
-  c->blk_off_h.push_back(words);
-  c->blk_off_h.push_back(bytes);
-  upload(c->blk, bl);
-  upload(c->blk_off, c->blk_off_h);
+  prep.blk_off_h.push_back(words);
+  prep.blk_off_h.push_back(bytes);
+  upload(prep.blk, bl);
+  upload(prep.blk_off, prep.blk_off_h);
   for (int d = 0; d < 2; d++) {
-    const Identities& I = c->ids[d];
+    const Identities& I = prep.ids[d];
     std::vector<uint32_t> ib(I.ns.size(), 0);
     std::vector<uint2> iw(I.ns.size(), uint2{0, 0});
     for (uint32_t q = 0; q < pb.P; q++) {
@@ -179,25 +172,25 @@ static void prepare_blocks_device(cyc_ctx* c) {
       ib[I.of_pod[q]] = pb.pod_blk[q];
       iw[I.of_pod[q]] = uint2{x.p0 / 64, (x.p1 + 63) / 64 - x.p0 / 64};
     }
-    upload(c->id_blk[d], ib);
-    upload(c->id_win[d], iw);
+    upload(prep.id_blk[d], ib);
+    upload(prep.id_win[d], iw);
   }
-  c->first_blk.alloc(std::max<uint64_t>(pb.blocks.size() * 8, 16));
+  prep.first_blk.alloc(std::max<uint64_t>(pb.blocks.size() * 8, 16));
 }
 
-static void prepare_device(cyc_ctx* c) {
-  Problem& pb = c->pb;
-  PhaseClock clk("prepare_device");
-  upload(c->ls_off, pb.ls_off);
-  upload(c->ls_key, pb.ls_key);
-  upload(c->ls_val, pb.ls_val);
-  upload(c->sel_off, pb.sel_off);
-  upload(c->reqs, pb.reqs);
-  upload(c->req_vals, pb.req_vals);
-  upload(c->pod_ns, pb.pod_ns);
-  upload(c->pod_ls, pb.pod_ls);
-  upload(c->pod_nsls, pb.pod_nsls);
-  upload(c->pod_ip, pb.pod_ip);
+// prepare_device's stages, each filling its part of a fresh Prepared from the problem (and the
+// identities build_identities left there).
+static void upload_tables(const Problem& pb, Prepared& prep) {
+  upload(prep.ls_off, pb.ls_off);
+  upload(prep.ls_key, pb.ls_key);
+  upload(prep.ls_val, pb.ls_val);
+  upload(prep.sel_off, pb.sel_off);
+  upload(prep.reqs, pb.reqs);
+  upload(prep.req_vals, pb.req_vals);
+  upload(prep.pod_ns, pb.pod_ns);
+  upload(prep.pod_ls, pb.pod_ls);
+  upload(prep.pod_nsls, pb.pod_nsls);
+  upload(prep.pod_ip, pb.pod_ip);
   {  // the address index of the range-built IP rows: IPv4 pods by address, then IPv6 pods
     std::vector<uint32_t> p4, p6;
     for (uint32_t q = 0; q < pb.P; q++)
@@ -205,13 +198,13 @@ static void prepare_device(cyc_ctx* c) {
     std::stable_sort(p4.begin(), p4.end(), [&](uint32_t x, uint32_t y) { return pb.pod_ip[x].w[3] < pb.pod_ip[y].w[3]; });
     auto a6 = [&](uint32_t q) { return std::array<uint32_t, 4>{pb.pod_ip[q].w[0], pb.pod_ip[q].w[1], pb.pod_ip[q].w[2], pb.pod_ip[q].w[3]}; };
     std::stable_sort(p6.begin(), p6.end(), [&](uint32_t x, uint32_t y) { return a6(x) < a6(y); });
-    c->ip4_key.resize(p4.size());
-    c->ip6_key.resize(p6.size());
-    for (size_t x = 0; x < p4.size(); x++) c->ip4_key[x] = pb.pod_ip[p4[x]].w[3];
-    for (size_t x = 0; x < p6.size(); x++) c->ip6_key[x] = a6(p6[x]);
-    c->ipsort_host = p4;
-    c->ipsort_host.insert(c->ipsort_host.end(), p6.begin(), p6.end());
-    upload(c->ipsort, c->ipsort_host);
+    prep.ip4_key.resize(p4.size());
+    prep.ip6_key.resize(p6.size());
+    for (size_t x = 0; x < p4.size(); x++) prep.ip4_key[x] = pb.pod_ip[p4[x]].w[3];
+    for (size_t x = 0; x < p6.size(); x++) prep.ip6_key[x] = a6(p6[x]);
+    prep.ipsort_host = p4;
+    prep.ipsort_host.insert(prep.ipsort_host.end(), p6.begin(), p6.end());
+    upload(prep.ipsort, prep.ipsort_host);
     // a family whose pods' addresses never decrease in pod order (addresses handed out in pod order:
     // configs #2-#4) sorts to pod order, so its sorted positions ARE its pods in pod order: a network's
     // pods of that family are then pod-index intervals (ip_rows_iv_blk)
@@ -220,38 +213,38 @@ static void prepare_device(cyc_ctx* c) {
         if (pods[x] < pods[x - 1]) return false;
       return true;
     };
-    c->ip_mono[0] = mono(p4);
-    c->ip_mono[1] = mono(p6);
+    prep.ip_mono[0] = mono(p4);
+    prep.ip_mono[1] = mono(p6);
   }
-  upload(c->cidrs, pb.cidrs);
-  upload(c->ipbs, pb.ipbs);
-  upload(c->ipb_ex, pb.ipb_ex);
-  upload(c->pms, pb.pms);
-  upload(c->pents, pb.pents);
-  upload(c->peers, pb.peers);
-  upload(c->descs, pb.descs);
-  upload(c->slot_desc, pb.slot_desc);
-  upload(c->slot_status, pb.slot_status);
-  upload(c->slot_cfg, pb.slot_cfg);
-  upload(c->slot_idx, pb.slot_idx);
-  clk.lap("uploads");
-  uint64_t R = pb.peers.size(), W = pb.W, D = std::max<size_t>(pb.descs.size(), 1), K = pb.K;
-  c->selres.alloc(std::max<uint64_t>(uint64_t(pb.S) * pb.L, 16));
+  upload(prep.cidrs, pb.cidrs);
+  upload(prep.ipbs, pb.ipbs);
+  upload(prep.ipb_ex, pb.ipb_ex);
+  upload(prep.pms, pb.pms);
+  upload(prep.pents, pb.pents);
+  upload(prep.peers, pb.peers);
+  upload(prep.descs, pb.descs);
+  upload(prep.slot_desc, pb.slot_desc);
+  upload(prep.slot_status, pb.slot_status);
+  upload(prep.slot_cfg, pb.slot_cfg);
+  upload(prep.slot_idx, pb.slot_idx);
+}
+
+static void build_label_tables(const Problem& pb, Prepared& prep) {
+  prep.selres.alloc(std::max<uint64_t>(uint64_t(pb.S) * pb.L, 16));
   {  // dense label table for k_selectors_dense: label keys -> dense index kx, LVT[kx][l]
     std::vector<int32_t> kx(pb.strings.size(), -1);
     uint32_t nk = 0;
     for (uint32_t k : pb.ls_key)
       if (kx[k] < 0) kx[k] = int32_t(nk++);
-    c->dense_sel = uint64_t(nk + 1) * pb.L * 4 <= (256ull << 20);
-    c->sel_one_h.clear();
-    if (c->dense_sel) {
+    prep.dense_sel = uint64_t(nk + 1) * pb.L * 4 <= (256ull << 20);
+    if (prep.dense_sel) {
       std::vector<uint32_t> lvt(uint64_t(nk + 1) * pb.L, 0xFFFFFFFFu);
       for (uint32_t l = 0; l < pb.L; l++)
         for (uint32_t x = pb.ls_off[l]; x < pb.ls_off[l + 1]; x++) lvt[uint64_t(kx[pb.ls_key[x]]) * pb.L + l] = pb.ls_val[x];
       std::vector<DReq> dr = pb.reqs;
       for (DReq& q : dr) q.key = (q.op != REQ_INVALID && q.key < kx.size() && kx[q.key] >= 0) ? uint32_t(kx[q.key]) : nk;
-      upload(c->lvt, lvt);
-      upload(c->dreqs, dr);
+      upload(prep.lvt, lvt);
+      upload(prep.dreqs, dr);
       {  // one-requirement selectors in a single record each (SelView::one)
         std::vector<uint4> one(std::max<size_t>(pb.S, 1), uint4{SEL_WALK, 0, 0, 0});
         for (uint32_t sid = 0; sid < pb.S; sid++) {
@@ -266,14 +259,12 @@ static void prepare_device(cyc_ctx* c) {
           const uint32_t vc = has_v ? (q.op == REQ_EQ || q.op == REQ_EQ_EMPTY ? 1u : q.vcnt) : 0u;
           one[sid] = uint4{q.op | (vc << 8), q.key, vc > 0 ? pb.req_vals[q.voff] : 0u, vc > 1 ? pb.req_vals[q.voff + 1] : 0u};
         }
-        upload(c->sel_one, one);
-        c->sel_one_h = one;
+        upload(prep.sel_one, one);
+        prep.sel_one_h = one;
       }
       // the same table per pod (PLVT, sparse pod-peer rows) is gathered on the device when a run
       // first needs it (ensure_plvt): IDO builds never read it, and it is (keys + 1) x P words
-      c->n_lkeys = nk;
-      c->plvt.alloc(0);
-      c->plvt_ready = false;
+      prep.n_lkeys = nk;
       // label postings: the pods under each (dense key, value) of their own labels, and per EQ / IN
       // (<= 2 values) requirement the postings of its values (pod_rows_post_blk)
       // (key, value, pod) triples sorted by (key, value), pods ascending within: two counting-sort
@@ -315,7 +306,7 @@ static void prepare_device(cyc_ctx* c) {
         return std::make_pair(uint32_t(lo - kv.begin()), uint32_t(hi - lo));
       };
       std::vector<uint4> rp(dr.size(), uint4{0, 0, 0, 0});
-      c->req_post_ok.assign(dr.size(), 0);
+      prep.req_post_ok.assign(dr.size(), 0);
       for (size_t r = 0; r < dr.size(); r++) {
         const DReq& q = dr[r];
         if (q.key >= nk || !(q.op == REQ_EQ || (q.op == REQ_IN && q.vcnt >= 1 && q.vcnt <= 2))) continue;
@@ -326,29 +317,31 @@ static void prepare_device(cyc_ctx* c) {
           rp[r].z = b.first;
           rp[r].w = b.second;
         }
-        c->req_post_ok[r] = 1;
+        prep.req_post_ok[r] = 1;
       }
-      upload(c->req_post, rp);
-      upload(c->post_pods, pods);
+      upload(prep.req_post, rp);
+      upload(prep.post_pods, pods);
     }
   }
-  clk.lap("label tables");
-  c->PM.alloc(std::max<uint64_t>(R * W * 8, 16));
-  c->ip_rng.alloc(std::max<uint64_t>(R * 16 + R * ((W + 63) / 64) * 4, 16));  // [R][4] word spans + chunk masks, then [R][W/64] cnz
-  c->ip_rng_clean = false;  // a new buffer: the next fused front fills it (no emit has reset it yet)
-  c->ER.alloc(pb.may_err ? std::max<uint64_t>(R * W * 8, 16) : 16);
+}
+
+static void build_peer_tables(const Problem& pb, Prepared& prep) {
+  const uint64_t R = pb.peers.size(), W = pb.W;
+  prep.PM.alloc(std::max<uint64_t>(R * W * 8, 16));
+  prep.ip_rng.alloc(std::max<uint64_t>(R * 16 + R * ((W + 63) / 64) * 4, 16));  // [R][4] word spans + chunk masks, then [R][W/64] cnz
+  prep.ER.alloc(pb.may_err ? std::max<uint64_t>(R * W * 8, 16) : 16);
   {
-    c->plan = plan_peers(pb, c->ids[1]);
-    PeerPlan& pl = c->plan;
-    upload(c->word_off, pl.word_off);
-    upload(c->run_e, pl.run_e);
-    upload(c->run_mask, pl.run_mask);
-    upload(c->runs, pl.runs);
-    upload(c->id_nsls, c->ids[1].nsls);
+    prep.plan = plan_peers(pb, prep.ids[1]);
+    PeerPlan& pl = prep.plan;
+    upload(prep.word_off, pl.word_off);
+    upload(prep.run_e, pl.run_e);
+    upload(prep.run_mask, pl.run_mask);
+    upload(prep.runs, pl.runs);
+    upload(prep.id_nsls, prep.ids[1].nsls);
     {  // per-word, per-family address intervals for k_ip_rows_fast, then one record per 64-word chunk
       const uint32_t NC = (pb.W + 63) / 64;
       std::vector<DWordIP> wi(pb.W + NC);
-      c->word_aff.assign(pb.W, 3);
+      prep.word_aff.assign(pb.W, 3);
       for (uint32_t w = 0; w < pb.W; w++) {
         DWordIP d{};
         d.min4 = 0xFFFFFFFFu;
@@ -391,7 +384,7 @@ static void prepare_device(cyc_ctx* c) {
         }
         for (int f = 0; f < 2; f++)
           if (first[f] >= 0 && aff[f]) d.aff |= (uint32_t(first[f]) | 0x80u) << (8 * f);
-        c->word_aff[w] = uint8_t((first[0] < 0 || aff[0] ? 1u : 0u) | (first[1] < 0 || aff[1] ? 2u : 0u));
+        prep.word_aff[w] = uint8_t((first[0] < 0 || aff[0] ? 1u : 0u) | (first[1] < 0 || aff[1] ? 2u : 0u));
         wi[w] = d;
       }
       for (uint32_t ch = 0; ch < NC; ch++) {
@@ -413,8 +406,8 @@ static void prepare_device(cyc_ctx* c) {
         }
         wi[pb.W + ch] = d;
       }
-      upload(c->ip_words, wi);
-      c->ipw_h = wi;
+      upload(prep.ip_words, wi);
+      prep.ipw_h = wi;
       // namespace range of every word's and chunk's pods (pod_rows_sparse_blk)
       std::vector<DWordNS> nw(pb.W + NC, DWordNS{0xFFFFFFFFu, 0u, 0u, 0u});
       for (uint32_t q = 0; q < pb.P; q++) {
@@ -425,12 +418,17 @@ static void prepare_device(cyc_ctx* c) {
           x->hi = std::max(x->hi, pb.pod_ns[q]);
         }
       }
-      upload(c->ns_words, nw);
+      upload(prep.ns_words, nw);
     }
-    c->ido.alloc(std::max<uint64_t>(uint64_t(pl.pod_peers.size()) * c->ids[1].ns.size(), 16));
-    c->idob.alloc(std::max<uint64_t>(uint64_t(pl.pod_peers.size()) * ((c->ids[1].ns.size() + 63) / 64) * 8, 16));
+    prep.ido.alloc(std::max<uint64_t>(uint64_t(pl.pod_peers.size()) * prep.ids[1].ns.size(), 16));
+    prep.idob.alloc(std::max<uint64_t>(uint64_t(pl.pod_peers.size()) * ((prep.ids[1].ns.size() + 63) / 64) * 8, 16));
   }
-  clk.lap("peer plan");
+}
+
+static void alloc_scratch(const Problem& pb, Prepared& prep) {
+  const uint64_t W = pb.W, D = std::max<size_t>(pb.descs.size(), 1), K = pb.K;
+  // identity-set records (DirDev::B) only where the identity-set route is possible: a fact of the prepare alone
+  const bool ido = ido_possible(route_in(Options{}, pb, prep, RangePlan{}));
   {  // one VALID descriptor per slot across all pods? (egress class rows then skip the per-word slot words)
     std::vector<int32_t> ud(std::max<uint32_t>(pb.K, 1), -1);
     bool uni = pb.P > 0 && pb.K > 0;
@@ -439,19 +437,19 @@ static void prepare_device(cyc_ctx* c) {
       for (uint32_t q = 0; q < pb.P && uni; q++)
         uni = pb.slot_status[size_t(q) * pb.K + k] == CYC_JOB_VALID && pb.slot_desc[size_t(q) * pb.K + k] == ud[k];
     }
-    c->uni_desc = uni;
-    upload(c->udesc, ud);
+    prep.uni_desc = uni;
+    upload(prep.udesc, ud);
   }
-  c->portok.alloc(std::max<uint64_t>(pb.pms.size() * D, 16));
-  c->portbits.alloc(std::max<uint64_t>(pb.pms.size() * 4, 16));
-  c->VALID.alloc(std::max<uint64_t>(K * W * 8, 16));
-  c->DESCW.alloc(std::max<uint64_t>(K * W * 4, 16));
-  c->DM.alloc(std::max<uint64_t>(K * D * W * 8, 16));
-  c->first_err.alloc(std::max<uint64_t>(uint64_t(pb.n_cfg) * 8, 16));  // per probe config (k_first_error)
-  c->status_sink.alloc(std::max<uint64_t>(uint64_t(pb.P) * K, 16));
+  prep.portok.alloc(std::max<uint64_t>(pb.pms.size() * D, 16));
+  prep.portbits.alloc(std::max<uint64_t>(pb.pms.size() * 4, 16));
+  prep.VALID.alloc(std::max<uint64_t>(K * W * 8, 16));
+  prep.DESCW.alloc(std::max<uint64_t>(K * W * 4, 16));
+  prep.DM.alloc(std::max<uint64_t>(K * D * W * 8, 16));
+  prep.first_err.alloc(std::max<uint64_t>(uint64_t(pb.n_cfg) * 8, 16));  // per probe config (k_first_error)
+  prep.status_sink.alloc(std::max<uint64_t>(uint64_t(pb.P) * K, 16));
   for (int d = 0; d < 2; d++) {
-    Identities& I = c->ids[d];
-    DirDev& dd = c->dir[d];
+    Identities& I = prep.ids[d];
+    DirDev& dd = prep.dir[d];
     dd.n = uint32_t(I.ns.size());
     dd.ht_cap = I.ht_cap;
     upload(dd.id_ns, I.ns);
@@ -469,16 +467,12 @@ static void prepare_device(cyc_ctx* c) {
     dd.err.alloc(std::max<uint64_t>(dd.n, 16));
     dd.ht_key.alloc(uint64_t(dd.ht_cap) * 16 + 16);  // [cap] 16-byte entries (key ~0 = empty, rep), counter
     HIPCHK(hipMemset(dd.ht_key.p, 0xFF, dd.ht_key.bytes));  // empty; afterwards every run's class rows empty it
-    if (!c->zeros.p) {
-      c->zeros.alloc(256);
-      HIPCHK(hipMemset(c->zeros.p, 0, 256));
-    }
     dd.reps.alloc(std::max<uint64_t>(dd.n * 4ull, 16));
     dd.class_of.alloc(std::max<uint64_t>(dd.n * 4ull, 16));
     dd.A.alloc(std::max<uint64_t>(uint64_t(dd.n) * K * W * 8, 16));
     if (pb.may_err) dd.AE.alloc(std::max<uint64_t>(uint64_t(dd.n) * K * W * 8, 16));
     else dd.AE.alloc(0);
-    dd.B.alloc(ido_possible(route_in(c)) ? std::max<uint64_t>(ido_b_bytes(c, d), 16) : 16);
+    dd.B.alloc(ido ? std::max<uint64_t>(ido_b_bytes(pb, prep, d), 16) : 16);
     {  // IP-peer list bounds per identity: the IP peers of its namespace's targets
       // (upper bound for both list uses: IDO builds list the IP peers, PM builds every peer)
       std::vector<uint32_t> ns_ip(pb.strings.size(), 0), off(dd.n + 1, 0);
@@ -489,15 +483,28 @@ static void prepare_device(cyc_ctx* c) {
       dd.ip_list.alloc(std::max<uint64_t>(uint64_t(off[dd.n]) * 16, 16));
     }
   }
+  prep.zeros.alloc(256);
+  HIPCHK(hipMemset(prep.zeros.p, 0, 256));
+}
+
+// Everything a prepare leaves on the device, into the fresh Prepared that holds the identities; the
+// route is resolved with no rows planned yet (the fresh RangePlan).
+static void prepare_device(cyc_ctx* c) {
+  PhaseClock clk("prepare_device");
+  upload_tables(c->pb, c->prep);
+  clk.lap("uploads");
+  build_label_tables(c->pb, c->prep);
+  clk.lap("label tables");
+  build_peer_tables(c->pb, c->prep);
+  clk.lap("peer plan");
+  alloc_scratch(c->pb, c->prep);
   clk.lap("scratch");
-  prepare_blocks_device(c);
-  c->order_lo = c->order_hi = -1;
-  c->order_src = false;
+  prepare_blocks_device(c->pb, c->prep);
   reroute(c);
 }
 
 // nonzero-chunk flags of the IP peers' PM rows, after the word spans and chunk masks in the ip_rng buffer
-static uint32_t* ip_cnz(cyc_ctx* c) { return c->ip_rng.as<uint32_t>() + 4 * c->pb.peers.size(); }
+static uint32_t* ip_cnz(cyc_ctx* c) { return c->prep.ip_rng.as<uint32_t>() + 4 * c->pb.peers.size(); }
 
 static unsigned grid1(uint64_t n, unsigned block) { return unsigned(std::min<uint64_t>((n + block - 1) / block, 1u << 20)); }
 
@@ -506,32 +513,34 @@ static unsigned grid1(uint64_t n, unsigned block) { return unsigned(std::min<uin
 // and it fits PLVT_MAX_BYTES; otherwise the rows read LVT through each pod's label set (SelView
 // with PLVT null), one more dependent load per pod.
 static void ensure_plvt(cyc_ctx* c, hipStream_t st) {
-  if (c->plvt_ready || !c->dense_sel || !c->route.pod_sparse) return;
-  const uint64_t n = uint64_t(c->n_lkeys + 1) * c->pb.P;
-  if (!n || n * 4 > (uint64_t(c->plvt_max_mb) << 20)) return;
-  c->plvt.alloc(n * 4);
-  k_plvt<<<grid1(n, 256), 256, 0, st>>>(c->lvt.as<uint32_t>(), c->pod_ls.as<uint32_t>(), c->pb.L, c->pb.P, n,
-                                        c->plvt.as<uint32_t>());
+  if (c->prep.plvt_ready || !c->prep.dense_sel || !c->route.pod_sparse) return;
+  const uint64_t n = uint64_t(c->prep.n_lkeys + 1) * c->pb.P;
+  if (!n || n * 4 > (uint64_t(c->opt.plvt_max_mb) << 20)) return;
+  c->prep.plvt.alloc(n * 4);
+  k_plvt<<<grid1(n, 256), 256, 0, st>>>(c->prep.lvt.as<uint32_t>(), c->prep.pod_ls.as<uint32_t>(), c->pb.L, c->pb.P, n,
+                                        c->prep.plvt.as<uint32_t>());
   HIPCHK(hipGetLastError());
-  c->plvt_ready = true;
+  c->prep.plvt_ready = true;
 }
 static SelView sel_view(cyc_ctx* c) {
   SelView v{};
-  v.selres = c->route.lazy_sel ? nullptr : c->selres.as<uint8_t>();
+  v.selres = c->route.lazy_sel ? nullptr : c->prep.selres.as<uint8_t>();
   v.L = c->pb.L;
-  v.sel_off = c->sel_off.as<uint32_t>();
-  v.req_vals = c->req_vals.as<uint32_t>();
-  v.LVT = c->lvt.as<uint32_t>();
-  v.dreqs = c->dreqs.as<DReq>();
-  v.PLVT = c->plvt_ready ? c->plvt.as<uint32_t>() : nullptr;  // null: pod -> label set -> LVT gathers
+  v.sel_off = c->prep.sel_off.as<uint32_t>();
+  v.req_vals = c->prep.req_vals.as<uint32_t>();
+  v.LVT = c->prep.lvt.as<uint32_t>();
+  v.dreqs = c->prep.dreqs.as<DReq>();
+  v.PLVT = c->prep.plvt_ready ? c->prep.plvt.as<uint32_t>() : nullptr;  // null: pod -> label set -> LVT gathers
   v.P = c->pb.P;
-  v.one = c->sel_one.as<uint4>();
+  v.one = c->prep.sel_one.as<uint4>();
   return v;
 }
 
 static MemberArgs member_args(cyc_ctx* c, int d) {
   Problem& pb = c->pb;
-  DirDev& dd = c->dir[d];
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
+  DirDev& dd = prep.dir[d];
   MemberArgs a{};
   a.n_ident = dd.n;
   a.L = pb.L;
@@ -551,12 +560,12 @@ static MemberArgs member_args(cyc_ctx* c, int d) {
   a.err = dd.err.as<uint8_t>();
   a.ht_key = dd.ht_key.as<unsigned long long>();
   a.ht_cap = dd.ht_cap;
-  a.act = c->act[d].as<uint32_t>();
-  a.actrec = c->actrec[d].as<uint4>();
-  a.n_act = c->n_act[d];
+  a.act = rp.act[d].as<uint32_t>();
+  a.actrec = rp.actrec[d].as<uint4>();
+  a.n_act = rp.n_act[d];
   a.reps = dd.reps.as<uint32_t>();
   a.rep_cnt = dd.rep_cnt();
-  a.id_blk = c->pb.blocks.empty() ? nullptr : c->id_blk[d].as<uint32_t>();
+  a.id_blk = c->pb.blocks.empty() ? nullptr : prep.id_blk[d].as<uint32_t>();
   return a;
 }
 
@@ -565,7 +574,7 @@ static MemberArgs member_args(cyc_ctx* c, int d) {
 // config #4's 13 chunks +9 %: profiles/r02_pl_threads_ab.txt) — and blocks per direction, striding
 // over the representatives, about two blocks in flight per CU slot
 static uint32_t pl_threads(const cyc_ctx* c) { return (c->pb.W + 63) / 64 >= 16 ? 256u : PL_THREADS; }
-static uint32_t pl_blocks(const cyc_ctx* c, int d) { return std::min<uint32_t>(c->n_act[d], 2048u * 256u / pl_threads(c)); }
+static uint32_t pl_blocks(const cyc_ctx* c, int d) { return std::min<uint32_t>(c->range.n_act[d], 2048u * 256u / pl_threads(c)); }
 
 // Range plan for rows [lo,hi): (1) the rows ordered so pods sharing class rows are adjacent
 // (L2 / Infinity-Cache reuse in k_emit); (2) the identities those rows use, per direction —
@@ -578,13 +587,13 @@ static uint32_t pl_blocks(const cyc_ctx* c, int d) { return std::min<uint32_t>(c
 // of 64 and hi too unless it is P (checked by the caller), so the windows of a partition tile the words.
 // Word window of direction d's peer rows in the current plan: [w0, w0 + nw); as 64-word chunks
 // [c0, c0 + nch).
-static void peer_window(const cyc_ctx* c, int d, uint32_t& w0, uint32_t& nw) {
-  w0 = d == 0 ? c->win_w0 : 0u;
-  nw = d == 0 ? c->win_wa : c->pb.W;
+static void peer_window(const RangePlan& rp, uint32_t W, int d, uint32_t& w0, uint32_t& nw) {
+  w0 = d == 0 ? rp.win_w0 : 0u;
+  nw = d == 0 ? rp.win_wa : W;
 }
-static void peer_chunks(const cyc_ctx* c, int d, uint32_t& c0, uint32_t& nch) {
+static void peer_chunks(const RangePlan& rp, uint32_t W, int d, uint32_t& c0, uint32_t& nch) {
   uint32_t w0, nw;
-  peer_window(c, d, w0, nw);
+  peer_window(rp, W, d, w0, nw);
   c0 = w0 / 64;
   nch = nw ? (w0 + nw + 63) / 64 - c0 : 0u;
 }
@@ -605,64 +614,62 @@ static bool ip_chunk_touch(const DCidr& n, const DWordIP& ck) {
   return ck.m6 && !(lt(ck.max6, lo) || lt(hi, ck.min6));
 }
 
-static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
-  if (c->order_lo == lo && c->order_hi == hi && c->order_src == src) return;
-  Problem& pb = c->pb;
-  PhaseClock clk("range plan");
-  c->order_lo = c->order_hi = -1;  // (no plan until this one is complete)
-  c->order_src = src;
-  c->rl[0] = src ? 0 : lo;
-  c->rh[0] = src ? int64_t(pb.P) : hi;
-  c->rl[1] = lo;
-  c->rh[1] = hi;
-  c->win_w0 = src ? uint32_t(lo / 64) : 0u;
-  c->win_wa = src ? uint32_t((hi + 63) / 64 - lo / 64) : pb.W;
-  if (src && hi <= lo) c->win_wa = 0;
+// Fills a fresh plan for rows [lo, hi) from the options, the problem and its prepare.
+static void build_range_plan(const Options& opt, const Problem& pb, const Prepared& prep, int64_t lo, int64_t hi, bool src,
+                             RangePlan& rp) {
+  rp.lo = lo, rp.hi = hi, rp.src = src;
+  rp.rl[0] = src ? 0 : lo;
+  rp.rh[0] = src ? int64_t(pb.P) : hi;
+  rp.rl[1] = lo;
+  rp.rh[1] = hi;
+  rp.win_w0 = src ? uint32_t(lo / 64) : 0u;
+  rp.win_wa = src ? uint32_t((hi + 63) / 64 - lo / 64) : pb.W;
+  if (src && hi <= lo) rp.win_wa = 0;
   {  // the egress identities of the window's pods (identity ids follow first appearance in pod order, so a
      // source shard's are mostly one range): the ingress identity sets need only their words
-    const uint32_t EW = uint32_t((c->ids[1].ns.size() + 63) / 64);
-    c->ido_ew0 = 0;
-    c->ido_ew1 = EW;
+    const uint32_t EW = uint32_t((prep.ids[1].ns.size() + 63) / 64);
+    rp.ido_ew0 = 0;
+    rp.ido_ew1 = EW;
     if (src) {
       uint32_t e0 = UINT32_MAX, e1 = 0;
-      for (int64_t q = c->win_w0 * 64ll; q < std::min<int64_t>(int64_t(c->win_w0 + c->win_wa) * 64, pb.P); q++) {
-        e0 = std::min(e0, c->ids[1].of_pod[size_t(q)]);
-        e1 = std::max(e1, c->ids[1].of_pod[size_t(q)] + 1);
+      for (int64_t q = rp.win_w0 * 64ll; q < std::min<int64_t>(int64_t(rp.win_w0 + rp.win_wa) * 64, pb.P); q++) {
+        e0 = std::min(e0, prep.ids[1].of_pod[size_t(q)]);
+        e1 = std::max(e1, prep.ids[1].of_pod[size_t(q)] + 1);
       }
-      c->ido_ew0 = e0 == UINT32_MAX ? 0u : e0 / 64;
-      c->ido_ew1 = e0 == UINT32_MAX ? 0u : (e1 + 63) / 64;
+      rp.ido_ew0 = e0 == UINT32_MAX ? 0u : e0 / 64;
+      rp.ido_ew1 = e0 == UINT32_MAX ? 0u : (e1 + 63) / 64;
     }
   }
-  // the answers that rest on the rows and window alone: the plan below is built by them (row phases:
-  // the emit lists hold the rows before the split first)
-  const Route by_window = resolve_route(route_in(c));
+  // the answers that rest on the rows and window alone (all rp holds so far): the plan below is built by
+  // them (row phases: the emit lists hold the rows before the split first)
+  const Route by_window = resolve_route(route_in(opt, pb, prep, rp));
   const uint32_t split = by_window.phase_split;
   for (int d = 0; d < 2; d++) {  // emit row order: clustered by this direction's identity, (pod, identity) pairs
-    std::vector<uint32_t> ord(size_t(c->rh[d] - c->rl[d]));
-    std::iota(ord.begin(), ord.end(), uint32_t(c->rl[d]));
-    const auto& i1 = c->ids[d].of_pod;
-    const auto& i2 = c->ids[1 - d].of_pod;
+    std::vector<uint32_t> ord(size_t(rp.rh[d] - rp.rl[d]));
+    std::iota(ord.begin(), ord.end(), uint32_t(rp.rl[d]));
+    const auto& i1 = prep.ids[d].of_pod;
+    const auto& i2 = prep.ids[1 - d].of_pod;
     std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
       if (split && (x < split) != (y < split)) return x < split;
       return i1[x] != i1[y] ? i1[x] < i1[y] : i2[x] < i2[y];
     });
-    c->phase_n1[d] = split ? split - uint32_t(c->rl[d]) : 0u;
+    rp.phase_n1[d] = split ? split - uint32_t(rp.rl[d]) : 0u;
     std::vector<uint32_t> pairs(ord.size() * 2);
     for (size_t r = 0; r < ord.size(); r++) {
       pairs[2 * r] = ord[r];
       pairs[2 * r + 1] = i1[ord[r]];
     }
-    upload(c->order[d], pairs);
+    upload(rp.order[d], pairs);
   }
   std::vector<uint8_t> peer_needed(pb.peers.size(), 0), peer_dir(pb.peers.size(), 0);
   for (const DTarget& t : pb.tgt[1])
     for (uint32_t j = t.poff; j < t.poff + t.pcnt; j++) peer_dir[j] = 1;
   for (int d = 0; d < 2; d++) {
-    const Identities& I = c->ids[d];
+    const Identities& I = prep.ids[d];
     std::vector<uint8_t> used(I.ns.size(), 0);
     std::vector<uint32_t> act;
-    const bool empty_window = d == 0 && c->win_wa == 0;  // a source shard without sources: no ingress words
-    for (int64_t p = c->rl[d]; p < c->rh[d] && !empty_window; p++) {
+    const bool empty_window = d == 0 && rp.win_wa == 0;  // a source shard without sources: no ingress words
+    for (int64_t p = rp.rl[d]; p < rp.rh[d] && !empty_window; p++) {
       uint32_t i = I.of_pod[size_t(p)];
       if (!used[i]) {
         used[i] = 1;
@@ -672,22 +679,22 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
     std::sort(act.begin(), act.end());
     {  // each active identity's first pod in the range: its plane row holds the class row in place
       std::vector<uint32_t> ar(I.ns.size(), 0xFFFFFFFFu);
-      for (int64_t p = c->rh[d] - 1; p >= c->rl[d]; p--) ar[I.of_pod[size_t(p)]] = uint32_t(p - c->rl[d]);
-      upload(c->arow[d], ar);
-      c->n_act_ph1[d] = 0;  // (row phases: the phase-1 launch's representatives are among these)
+      for (int64_t p = rp.rh[d] - 1; p >= rp.rl[d]; p--) ar[I.of_pod[size_t(p)]] = uint32_t(p - rp.rl[d]);
+      upload(rp.arow[d], ar);
+      rp.n_act_ph1[d] = 0;  // (row phases: the phase-1 launch's representatives are among these)
       for (uint32_t i : act)
-        if (split && ar[i] < split) c->n_act_ph1[d]++;
+        if (split && ar[i] < split) rp.n_act_ph1[d]++;
     }
     std::vector<uint8_t> ns_needed(pb.strings.size(), 0);
     for (uint32_t i : act) ns_needed[I.ns[i]] = 1;
     for (const DTarget& t : pb.tgt[d])
       if (ns_needed[t.ns])
         for (uint32_t j = t.poff; j < t.poff + t.pcnt; j++) peer_needed[j] = 1;
-    c->n_act[d] = uint32_t(act.size());
+    rp.n_act[d] = uint32_t(act.size());
     uint64_t tsum = 0;  // namespace targets each active identity's membership walk visits
     for (uint32_t i : act) tsum += pb.tns_hi[d][I.ns[i]] - pb.tns_lo[d][I.ns[i]];
-    c->act_targets[d] = act.empty() ? 0.0 : double(tsum) / double(act.size());
-    upload(c->act[d], act);
+    rp.act_targets[d] = act.empty() ? 0.0 : double(tsum) / double(act.size());
+    upload(rp.act[d], act);
     // the membership's per-identity inputs in one 16-byte record (one load instead of the chain
     // act -> id_ls / id_ns / list_off -> tns_lo / tns_hi)
     std::vector<uint32_t> rec(act.size() * 4);
@@ -698,7 +705,7 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
       rec[4 * x + 2] = pb.tns_hi[d][ns];
       rec[4 * x + 3] = I.list_off[i];
     }
-    upload(c->actrec[d], rec);
+    upload(rp.actrec[d], rec);
   }
   // selectors the range can reach: its targets' pod selectors and their peers' selectors
   std::vector<uint8_t> sel_needed(pb.S, 0);
@@ -709,9 +716,9 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
       if (needed || t.pcnt == 0) sel_needed[t.sel] = 1;
     }
   for (int d = 0; d < 2; d++) {  // targets of active namespaces (also those without peers)
-    const Identities& I = c->ids[d];
+    const Identities& I = prep.ids[d];
     std::vector<uint8_t> ns_needed(pb.strings.size(), 0);
-    for (int64_t p = c->rl[d]; p < c->rh[d]; p++) ns_needed[I.ns[I.of_pod[size_t(p)]]] = 1;
+    for (int64_t p = rp.rl[d]; p < rp.rh[d]; p++) ns_needed[I.ns[I.of_pod[size_t(p)]]] = 1;
     for (const DTarget& t : pb.tgt[d])
       if (ns_needed[t.ns]) sel_needed[t.sel] = 1;
   }
@@ -723,30 +730,30 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
   std::vector<uint32_t> sl;
   for (uint32_t i = 0; i < pb.S; i++)
     if (sel_needed[i]) sl.push_back(i);
-  c->n_sel = uint32_t(sl.size());
+  rp.n_sel = uint32_t(sl.size());
   {  // sparse pod rows: peers whose pod selector is one posting requirement are built from postings
     // (ingress peers first, then egress: each sub-list has its direction's word window)
     std::vector<uint32_t> scan, post;
     for (int d = 0; d < 2; d++) {
-      c->scan_off[d] = uint32_t(scan.size());
-      c->post_off[d] = uint32_t(post.size());
-      for (uint32_t j : c->plan.pod_peers) {
+      rp.scan_off[d] = uint32_t(scan.size());
+      rp.post_off[d] = uint32_t(post.size());
+      for (uint32_t j : prep.plan.pod_peers) {
         if (!peer_needed[j] || peer_dir[j] != d) continue;
         const DPeer& pr = pb.peers[j];
         if (pr.nskind == NS_ALL && pr.podsel == CYC_ALL) continue;  // all-ones row: the class rows need none
         const bool one = pr.podsel != CYC_ALL && pb.sel_off[pr.podsel + 1] - pb.sel_off[pr.podsel] == 1;
-        if (one && c->dense_sel && !c->req_post_ok.empty() && c->req_post_ok[pb.sel_off[pr.podsel]]) post.push_back(j);
+        if (one && prep.dense_sel && !prep.req_post_ok.empty() && prep.req_post_ok[pb.sel_off[pr.podsel]]) post.push_back(j);
         else scan.push_back(j);
       }
     }
-    c->scan_off[2] = uint32_t(scan.size());
-    c->post_off[2] = uint32_t(post.size());
-    c->n_scan = uint32_t(scan.size());
-    c->n_post = uint32_t(post.size());
-    upload(c->pp_scan, scan);
-    upload(c->pp_post, post);
+    rp.scan_off[2] = uint32_t(scan.size());
+    rp.post_off[2] = uint32_t(post.size());
+    rp.n_scan = uint32_t(scan.size());
+    rp.n_post = uint32_t(post.size());
+    upload(rp.pp_scan, scan);
+    upload(rp.pp_post, post);
   }
-  upload(c->sel_list, sl);
+  upload(rp.sel_list, sl);
   std::vector<uint32_t> pp, ip;
   std::vector<DIPTest> tests;
   // An IP peer's row depends only on its IPBlock (ippeermatcher.go:43-50; the port is tested by the
@@ -760,21 +767,21 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
   // an IPBlock's matching pods as intervals of the address index (its family's block, less each
   // same-family except), their count and word span: built from ranges when few and close
   // (no-panic runs only: the ordered walk with panic bits keeps its dense rows)
-  const uint32_t n4 = uint32_t(c->ip4_key.size());
+  const uint32_t n4 = uint32_t(prep.ip4_key.size());
   // a network's pods of its family as positions [a, b) of the address index (ipsort_host)
   auto bounds = [&](const DCidr& cd, uint32_t& a, uint32_t& b) {
     if (cd.fam == 4) {
       const uint32_t lo = cd.net[3] & cd.mask[3], hi = lo | ~cd.mask[3];
-      a = uint32_t(std::lower_bound(c->ip4_key.begin(), c->ip4_key.end(), lo) - c->ip4_key.begin());
-      b = uint32_t(std::upper_bound(c->ip4_key.begin(), c->ip4_key.end(), hi) - c->ip4_key.begin());
+      a = uint32_t(std::lower_bound(prep.ip4_key.begin(), prep.ip4_key.end(), lo) - prep.ip4_key.begin());
+      b = uint32_t(std::upper_bound(prep.ip4_key.begin(), prep.ip4_key.end(), hi) - prep.ip4_key.begin());
     } else {
       std::array<uint32_t, 4> lo, hi;
       for (int i = 0; i < 4; i++) {
         lo[i] = cd.net[i] & cd.mask[i];
         hi[i] = lo[i] | ~cd.mask[i];
       }
-      a = n4 + uint32_t(std::lower_bound(c->ip6_key.begin(), c->ip6_key.end(), lo) - c->ip6_key.begin());
-      b = n4 + uint32_t(std::upper_bound(c->ip6_key.begin(), c->ip6_key.end(), hi) - c->ip6_key.begin());
+      a = n4 + uint32_t(std::lower_bound(prep.ip6_key.begin(), prep.ip6_key.end(), lo) - prep.ip6_key.begin());
+      b = n4 + uint32_t(std::upper_bound(prep.ip6_key.begin(), prep.ip6_key.end(), hi) - prep.ip6_key.begin());
     }
   };
   // ipaddress.go:22-40 on the index: the CIDR's positions less each same-family except's (an except of
@@ -783,7 +790,7 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
     iv.assign(1, uint2{});
     bounds(t.cidr, iv[0].x, iv[0].y);
     for (uint32_t e = 0; e < t.excnt; e++) {
-      const DCidr& x = c->plan.ip_ex[t.exoff + e];
+      const DCidr& x = prep.plan.ip_ex[t.exoff + e];
       if (!x.valid) return false;
       if (x.fam != t.cidr.fam) continue;
       uint32_t ea, eb;
@@ -806,15 +813,15 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
   std::vector<DIPIv> vtests;
   std::vector<uint2> viv;
   auto iv_rows = [&](const DIPTest& t, DIPIv& out) -> bool {
-    if (pb.may_err || !t.cidr.valid || c->ip_iv == 0 || !c->ip_mono[t.cidr.fam == 4 ? 0 : 1]) return false;
+    if (pb.may_err || !t.cidr.valid || opt.ip_iv == 0 || !prep.ip_mono[t.cidr.fam == 4 ? 0 : 1]) return false;
     std::vector<uint2> iv;
     if (!index_intervals(t, iv) || iv.size() > IPV_MAX) return false;
     out = DIPIv{t.peer, t.cidr.fam == 4 ? 0u : 1u, uint32_t(viv.size()), uint32_t(iv.size())};
-    for (const uint2& v : iv) viv.push_back(make_uint2(c->ipsort_host[v.x], c->ipsort_host[v.y - 1] + 1));
+    for (const uint2& v : iv) viv.push_back(make_uint2(prep.ipsort_host[v.x], prep.ipsort_host[v.y - 1] + 1));
     return true;
   };
   auto range_rows = [&](const DIPTest& t, DIPRange& out) -> bool {
-    if (pb.may_err || !t.cidr.valid || c->ip_range == 0) return false;
+    if (pb.may_err || !t.cidr.valid || opt.ip_range == 0) return false;
     std::vector<uint2> iv;
     if (!index_intervals(t, iv)) return false;
     uint64_t n = 0;
@@ -823,32 +830,32 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
     uint32_t wlo = 0xFFFFFFFFu, whi = 0;
     for (const uint2& v : iv)
       for (uint32_t x = v.x; x < v.y; x++) {
-        wlo = std::min(wlo, c->ipsort_host[x] / 64);
-        whi = std::max(whi, c->ipsort_host[x] / 64);
+        wlo = std::min(wlo, prep.ipsort_host[x] / 64);
+        whi = std::max(whi, prep.ipsort_host[x] / 64);
       }
     if (n && whi - wlo >= IPR_SPAN) return false;
     // words whose pods of the family hold affine addresses get the network's lanes from its bounds
     // in k_ip_rows_fast (no per-pod test): keep those rows there (config #4: range-built rows
     // made launch B 64 -> 70 us; config #2's addresses step by 256, so its words are not affine)
     const uint8_t fbit = t.cidr.fam == 4 ? 1u : 2u;
-    bool all_aff = c->word_aff.size() == pb.W;
-    for (uint32_t w = wlo; all_aff && n && w <= whi; w++) all_aff = (c->word_aff[w] & fbit) != 0;
-    if (all_aff && c->ip_range < 0) return false;
+    bool all_aff = prep.word_aff.size() == pb.W;
+    for (uint32_t w = wlo; all_aff && n && w <= whi; w++) all_aff = (prep.word_aff[w] & fbit) != 0;
+    if (all_aff && opt.ip_range < 0) return false;
     out = DIPRange{t.peer, uint32_t(riv.size()), uint32_t(iv.size()), n ? wlo : 0u};
     riv.insert(riv.end(), iv.begin(), iv.end());
     return true;
   };
   for (int d = 0; d < 2; d++) {  // ingress peers first, then egress: one sub-list per branch
-    c->rp_off[d] = uint32_t(pp.size());
-    c->ri_off[d] = uint32_t(ip.size());
-    c->rr_off[d] = uint32_t(rtests.size());
-    c->rv_off[d] = uint32_t(vtests.size());
-    for (uint32_t j : c->plan.pod_peers)
+    rp.rp_off[d] = uint32_t(pp.size());
+    rp.ri_off[d] = uint32_t(ip.size());
+    rp.rr_off[d] = uint32_t(rtests.size());
+    rp.rv_off[d] = uint32_t(vtests.size());
+    for (uint32_t j : prep.plan.pod_peers)
       if (peer_needed[j] && peer_dir[j] == d) pp.push_back(j);
     std::map<std::vector<uint32_t>, uint32_t> ipb_row;
     std::vector<uint32_t> key;
-    for (size_t r = 0; r < c->plan.ip_peers.size(); r++) {
-      const uint32_t j = c->plan.ip_peers[r];
+    for (size_t r = 0; r < prep.plan.ip_peers.size(); r++) {
+      const uint32_t j = prep.plan.ip_peers[r];
       if (!peer_needed[j] || peer_dir[j] != d) continue;
       const DIPBlock& b = pb.ipbs[pb.peers[j].ipb];
       key.assign(1, b.cidr);
@@ -859,34 +866,34 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
         continue;
       }
       DIPIv vt{};
-      if (iv_rows(c->plan.ip_tests[r], vt)) {
+      if (iv_rows(prep.plan.ip_tests[r], vt)) {
         vtests.push_back(vt);
         continue;
       }
       DIPRange rt{};
-      if (range_rows(c->plan.ip_tests[r], rt)) {
+      if (range_rows(prep.plan.ip_tests[r], rt)) {
         rtests.push_back(rt);
         continue;
       }
       ip.push_back(j);
-      tests.push_back(c->plan.ip_tests[r]);
+      tests.push_back(prep.plan.ip_tests[r]);
     }
   }
-  c->rr_off[2] = uint32_t(rtests.size());
-  c->Rr = uint32_t(rtests.size());
-  upload(c->ipr_tests, rtests);
-  upload(c->ipr_iv, riv);
-  c->rv_off[2] = uint32_t(vtests.size());
-  c->Rv = uint32_t(vtests.size());
-  upload(c->ipv_tests, vtests);
-  upload(c->ipv_iv, viv);
-  upload(c->peer_row, prow);
-  c->prow_host = prow;
-  c->rp_off[2] = uint32_t(pp.size());
-  c->ri_off[2] = uint32_t(ip.size());
-  c->Rp = uint32_t(pp.size());
-  c->Ri = uint32_t(ip.size());
-  upload(c->pod_peers, pp);
+  rp.rr_off[2] = uint32_t(rtests.size());
+  rp.Rr = uint32_t(rtests.size());
+  upload(rp.ipr_tests, rtests);
+  upload(rp.ipr_iv, riv);
+  rp.rv_off[2] = uint32_t(vtests.size());
+  rp.Rv = uint32_t(vtests.size());
+  upload(rp.ipv_tests, vtests);
+  upload(rp.ipv_iv, viv);
+  upload(rp.peer_row, prow);
+  rp.prow_host = prow;
+  rp.rp_off[2] = uint32_t(pp.size());
+  rp.ri_off[2] = uint32_t(ip.size());
+  rp.Rp = uint32_t(pp.size());
+  rp.Ri = uint32_t(ip.size());
+  upload(rp.pod_peers, pp);
   {
     // IDOB rows depend on a pod peer only through (namespace matcher, pod selector)
     // (podpeermatcher.go:21-28; the port is checked per peer by the class rows), so peers sharing
@@ -897,10 +904,10 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
     std::vector<uint32_t> pi(std::max<size_t>(pb.peers.size(), 1), 0), ppu;
     std::vector<uint2> gns;
     for (int d = 0; d < 2; d++) {
-      c->rpu_off[d] = uint32_t(ppu.size());
-      c->ido_goff[d] = uint32_t(gns.size());
+      rp.rpu_off[d] = uint32_t(ppu.size());
+      rp.ido_goff[d] = uint32_t(gns.size());
       std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> row;  // matcher -> its first peer
-      for (uint32_t x = c->rp_off[d]; x < c->rp_off[d + 1]; x++) {
+      for (uint32_t x = rp.rp_off[d]; x < rp.rp_off[d + 1]; x++) {
         const DPeer& pr = pb.peers[pp[x]];
         row.emplace(std::make_tuple(pr.nskind, pr.nsval, pr.podsel), pp[x]);
       }
@@ -910,7 +917,7 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
         at[kv.first] = uint32_t(ppu.size());
         ppu.push_back(kv.second);
       }
-      for (uint32_t x = c->rp_off[d]; x < c->rp_off[d + 1]; x++) {
+      for (uint32_t x = rp.rp_off[d]; x < rp.rp_off[d + 1]; x++) {
         const DPeer& pr = pb.peers[pp[x]];
         pi[pp[x]] = at[std::make_tuple(pr.nskind, pr.nsval, pr.podsel)];
       }
@@ -926,34 +933,34 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
         gns.push_back(r);
       }
     }
-    c->rpu_off[2] = uint32_t(ppu.size());
-    upload(c->pod_peers_u, ppu);
+    rp.rpu_off[2] = uint32_t(ppu.size());
+    upload(rp.pod_peers_u, ppu);
     {  // the rows' matcher records (pb_rec), read by the identity-set waves when selectors are evaluated there
       std::vector<uint4> rec(std::max<size_t>(ppu.size(), 1) * 3, uint4{0, 0, 0, 0});
-      const bool one = c->sel_one_h.size() >= std::max<size_t>(pb.S, 1);
+      const bool one = prep.sel_one_h.size() >= std::max<size_t>(pb.S, 1);
       for (size_t x = 0; one && x < ppu.size(); x++) {
         const DPeer& pr = pb.peers[ppu[x]];
         rec[3 * x] = uint4{pr.nskind, pr.nsval, pr.podsel, 0u};
-        rec[3 * x + 1] = pr.nskind == 2 ? c->sel_one_h[pr.nsval] : uint4{SEL_ALL, 0u, 0u, 0u};
-        rec[3 * x + 2] = pr.podsel != CYC_ALL ? c->sel_one_h[pr.podsel] : uint4{SEL_ALL, 0u, 0u, 0u};
+        rec[3 * x + 1] = pr.nskind == 2 ? prep.sel_one_h[pr.nsval] : uint4{SEL_ALL, 0u, 0u, 0u};
+        rec[3 * x + 2] = pr.podsel != CYC_ALL ? prep.sel_one_h[pr.podsel] : uint4{SEL_ALL, 0u, 0u, 0u};
       }
-      if (one) upload(c->pb_rec, rec);
-      else c->pb_rec.alloc(0);
+      if (one) upload(rp.pb_rec, rec);
+      else rp.pb_rec.alloc(0);
     }
-    upload(c->peer_ido, pi);
+    upload(rp.peer_ido, pi);
     gns.push_back(uint2{0u, 0xFFFFFFFFu});
-    upload(c->ido_grp_ns, gns);
-    const auto& ins = c->ids[1].ns;  // egress identities' namespaces, per 64-identity word
+    upload(rp.ido_grp_ns, gns);
+    const auto& ins = prep.ids[1].ns;  // egress identities' namespaces, per 64-identity word
     std::vector<uint2> wns(std::max<size_t>((ins.size() + 63) / 64, 1), uint2{0xFFFFFFFFu, 0u});
     for (size_t e = 0; e < ins.size(); e++) {
       wns[e / 64].x = std::min(wns[e / 64].x, ins[e]);
       wns[e / 64].y = std::max(wns[e / 64].y, ins[e]);
     }
-    upload(c->ido_word_ns, wns);
+    upload(rp.ido_word_ns, wns);
   }
-  upload(c->ip_peers, ip);
-  upload(c->ip_tests, tests);
-  upload(c->ip_ex, c->plan.ip_ex);
+  upload(rp.ip_peers, ip);
+  upload(rp.ip_tests, tests);
+  upload(rp.ip_ex, prep.plan.ip_ex);
   {  // IP-row work items of the fused front's segments (ip_rows_items_blk): per chunk of a segment's
      // window, its rows whose network meets the chunk's addresses (the chunk test of
      // ip_rows_fast_blk), IPI_TOUCH to a wave, and the others 64 to a wave (their chunk flags cleared)
@@ -965,18 +972,18 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
     // (config #3 rank 0 of 8: B 45.5 vs 20.9 us source, 36.4 vs 17.0 target; whole step +20 us), while
     // whole tables gain 0-1 % (profiles/r05_ip_items_ab.txt)
     const bool whole = lo == 0 && hi == int64_t(pb.P);
-    const bool on = (c->ip_items_opt == 1 || (c->ip_items_opt == -1 && whole)) && c->ipw_h.size() == size_t(pb.W) + NCH &&
+    const bool on = (opt.ip_items == 1 || (opt.ip_items == -1 && whole)) && prep.ipw_h.size() == size_t(pb.W) + NCH &&
                     !pb.may_err;
     for (int x = 0; x < 2; x++) {
-      c->ipi_off[x] = uint32_t(items.size());
+      rp.ipi_off[x] = uint32_t(items.size());
       if (!on || (one && x)) continue;
       const int dlo = one ? 0 : x, dhi = one ? 2 : x + 1;
-      const uint32_t i0 = c->ri_off[dlo], n = c->ri_off[dhi] - i0;
+      const uint32_t i0 = rp.ri_off[dlo], n = rp.ri_off[dhi] - i0;
       uint32_t c0, nch;
-      peer_chunks(c, one ? 1 : x, c0, nch);
+      peer_chunks(rp, pb.W, one ? 1 : x, c0, nch);
       std::vector<uint32_t> hit, miss;
       for (uint32_t ch = c0; n && ch < c0 + nch; ch++) {
-        const DWordIP& ck = c->ipw_h[pb.W + ch];
+        const DWordIP& ck = prep.ipw_h[pb.W + ch];
         hit.clear();
         miss.clear();
         for (uint32_t r = 0; r < n; r++) (ip_chunk_touch(tests[i0 + r].cidr, ck) ? hit : miss).push_back(r);
@@ -990,13 +997,19 @@ static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
         }
       }
     }
-    c->ipi_off[2] = uint32_t(items.size());
-    c->ip_items = on && !items.empty();
-    upload(c->ipi_items, items);
-    upload(c->ipi_list, il);
+    rp.ipi_off[2] = uint32_t(items.size());
+    rp.ip_items = on && !items.empty();
+    upload(rp.ipi_items, items);
+    upload(rp.ipi_list, il);
   }
+}
+
+static void ensure_range(cyc_ctx* c, int64_t lo, int64_t hi, bool src = false) {
+  if (c->range.is(lo, hi, src)) return;
+  PhaseClock clk("range plan");
+  c->range = RangePlan{};  // (the old plan's buffers go first; no plan is valid until this one is complete)
+  build_range_plan(c->opt, c->pb, c->prep, lo, hi, src, c->range);
   clk.lap("done");
-  c->order_lo = lo;
-  c->order_hi = hi;
+  c->range.valid = true;
   reroute(c);  // (the plan's facts are complete: the route of this prepare, option set, row range and partition)
 }

@@ -360,7 +360,10 @@ const char* cyc_block_error(const cyc_ctx* ctx, int64_t block);
  * stream: [0] whole pipeline, [1] the emit launch (the HBM-roofline kernel; one launch writes both
  * planes), [2] class rows of both directions.  Eager runs ("graphs" = 0) always record them; graph
  * and fused-eager runs only with "step_events" = 1, and report only [0] ([1], [2] = -1); without
- * events the call fails with CYC_ERR_ARG. */
+ * events the call fails with CYC_ERR_ARG.
+ * cyc_last_timings, cyc_last_classes and cyc_last_emit answer for runs of the current prepare only:
+ * after a cyc_probe_prepare* and before the next run they fail with CYC_ERR_ARG ("no run yet"), and
+ * "row_phases_active" reads 0. */
 int cyc_last_timings(cyc_ctx* ctx, double* ms, int n);
 
 /* Diagnostic: number of distinct classes (class rows computed) of the last run, [0] ingress,
@@ -388,7 +391,7 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  *                 rows through identity outcomes and word runs (0) or per pod (1)
  *   "member_wave" -1 (default: auto = 1 for <= 4096 identities) / 0 / 1: target membership with a
  *                 thread (0) or a wave (1) per pod identity
- *   "class_rpb"   4 (default, 1..64): class representatives per identity-set class-row block
+ *   "class_rpb"   0 (default: auto) / 1..64: class representatives per identity-set class-row block
  *   "step_events" 0 (default) / 1: graph and fused-eager runs also record the whole-step timing
  *                 events cyc_last_timings reads (they idle the GPU ~9 us between steps)
  *   "pl_wave"     1 (default) / 0: materialised-row class rows a wave per 64-word chunk where they
@@ -404,6 +407,8 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  *                 membership and pod-peer rows / identity sets use them (1) instead of as the dense
  *                 selector x label-set table first (0); auto = 1 for identity-set builds and once
  *                 that table has >= 64M pairs
+ *   "ip_range"    -1 (default: auto = where the words' addresses are not affine) / 0 / 1: IP rows of
+ *                 few, close pods built from the address index wherever they fit (1), or never (0)
  *   "ip_iv"       -1 (default: auto) / 0: IP rows as pod-index intervals where the network's family holds
  *                 non-decreasing addresses in pod order (ip_rows_iv_blk), or through the paths below
  *   "ip_items"    -1 (default: auto = 1 for runs over every row) / 0 / 1: the fused front's IP rows as
@@ -416,10 +421,13 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  *                 emit, then the other classes and rows [P/2, P)) or in one pass (1); the fused front
  *                 runs once either way (phase 1's emit on a second stream under phase 2's class rows
  *                 was 4-7 % slower: profiles/r06_row_phases_ab.txt)
+ *   "plvt_max_mb" 1024 (default) / 0..1048576: the largest per-pod label table (PLVT) the sparse pod-peer
+ *                 rows build on the device; beyond it (0: always) they gather through each pod's label set
  * cyc_get_option also reports "launch" (the graphs mode in effect), "row_phases_active" (the last
- * run's phases: 2, or 0), "front_fused_active" and
- * "pl_wave_active" (all need cyc_probe_prepare); "pod_words" reports the mode the prepared probe
- * uses (0 or 1). */
+ * run's phases: 2, or 0), "front_fused_active", "pl_wave_active" (needs cyc_probe_prepare),
+ * "class_inplace_active" (needs a run), "plvt_active" and "ip_iv_rows" (the current range plan's
+ * interval-built IP rows); "pod_words" reports the mode the prepared probe uses (0 or 1; needs
+ * cyc_probe_prepare). */
 int cyc_set_option(cyc_ctx* ctx, const char* name, int64_t value);
 int cyc_get_option(cyc_ctx* ctx, const char* name, int64_t* value);
 

@@ -50,9 +50,9 @@ static void member_wave() {
   EXPECT(in, member_wave[1], 0);
   in.n_act[1] = 4096, in.act_targets[1] = 3.999;
   EXPECT(in, member_wave[1], 0);
-  in.member_wave = 0;
+  in.opt.member_wave = 0;
   EXPECT(in, member_wave[0], 0);
-  in.member_wave = 1;
+  in.opt.member_wave = 1;
   EXPECT(in, member_wave[1], 1);
 }
 
@@ -62,9 +62,9 @@ static void pod_direct() {
   EXPECT(in, pod_direct, 1);
   in.P = 1201;  // 2 E == P - 1
   EXPECT(in, pod_direct, 0);
-  in.pod_rows = 1;
+  in.opt.pod_rows = 1;
   EXPECT(in, pod_direct, 1);
-  in.P = 1200, in.pod_rows = 0;
+  in.P = 1200, in.opt.pod_rows = 0;
   EXPECT(in, pod_direct, 0);
 }
 
@@ -81,10 +81,10 @@ static void pod_sparse() {
   EXPECT(in, pod_sparse, 1);
   in = pm_base();
   EXPECT(in, pod_sparse, 0);
-  in.pr_group = 8;
+  in.opt.pr_group = 8;
   EXPECT(in, pod_sparse, 1);
   in = ido_base();  // never with identity sets
-  in.pr_group = 8;
+  in.opt.pr_group = 8;
   in.W = in.win_wa = 1 << 11, in.rp_off[2] = 4096;
   EXPECT(in, ido, 1);
   EXPECT(in, pod_sparse, 0);
@@ -96,7 +96,7 @@ static void lazy_sel() {
   EXPECT(in, lazy_sel, 0);  // pod peers, a small table: dense
   in.rp_off[1] = in.rp_off[2] = 0;  // no pod peers, auto
   EXPECT(in, lazy_sel, 1);
-  in.sel_lazy = 0;
+  in.opt.sel_lazy = 0;
   EXPECT(in, lazy_sel, 0);
   in = pm_base();
   in.n_sel = 1 << 13, in.L = 1 << 13;  // 64M pairs
@@ -107,16 +107,16 @@ static void lazy_sel() {
   EXPECT(in, lazy_sel, 0);
   in.n_sel = 1 << 26;
   EXPECT(in, lazy_sel, 1);
-  in.sel_lazy = 0;
+  in.opt.sel_lazy = 0;
   EXPECT(in, lazy_sel, 0);
   in = pm_base();
-  in.sel_lazy = 1;
+  in.opt.sel_lazy = 1;
   EXPECT(in, lazy_sel, 1);
   in.may_err = true;  // never when a panic is possible
   EXPECT(in, lazy_sel, 0);
-  in.may_err = false, in.front_fused = 0;  // ... or when the front is not fused
+  in.may_err = false, in.opt.front_fused = 0;  // ... or when the front is not fused
   EXPECT(in, lazy_sel, 0);
-  in.front_fused = 1, in.dense_sel = false;  // ... or without the dense label table
+  in.opt.front_fused = 1, in.dense_sel = false;  // ... or without the dense label table
   EXPECT(in, fused, 0);
   EXPECT(in, lazy_sel, 0);
   in.n_sel = 0;  // (no selectors at all: fused, still not lazy without dense_sel)
@@ -124,7 +124,7 @@ static void lazy_sel() {
   EXPECT(in, lazy_sel, 0);
   in = ido_base();
   EXPECT(in, lazy_sel, 1);
-  in.sel_lazy = 0;
+  in.opt.sel_lazy = 0;
   EXPECT(in, lazy_sel, 0);
 }
 
@@ -140,9 +140,9 @@ static void ido() {
   in.blocks = true;
   EXPECT(in, ido, 0);
   in = ido_base();
-  in.pod_words = 0;
+  in.opt.pod_words = 0;
   EXPECT(in, ido, 0);
-  in.pod_words = 1;
+  in.opt.pod_words = 1;
   EXPECT(in, ido, 1);
   in.max_runs = IDO_MAX_RUNS + 1;  // forcing cannot make it possible
   EXPECT(in, ido, 0);
@@ -175,9 +175,9 @@ static void pl_wave() {
   EXPECT(in, pl_wave, 0);
   in.n_desc = PL_NB, in.W = 4097;
   EXPECT(in, pl_wave, 0);
-  in.W = 4096, in.pl_wave = 0;
+  in.W = 4096, in.opt.pl_wave = 0;
   EXPECT(in, pl_wave, 0);
-  in.pl_wave = 1, in.n_pm = 0;
+  in.opt.pl_wave = 1, in.n_pm = 0;
   EXPECT(in, pl_wave, 0);
   in.n_pm = 3, in.n_desc = 0;
   EXPECT(in, pl_wave, 0);
@@ -195,7 +195,7 @@ static void pl_wave() {
 static void fused() {
   RouteIn in = pm_base();
   EXPECT(in, fused, 1);
-  in.front_fused = 0;
+  in.opt.front_fused = 0;
   EXPECT(in, fused, 0);
   in = pm_base();
   in.may_err = true;
@@ -217,9 +217,9 @@ static void fused() {
   in = pm_base();
   in.E = 499, in.max_runs = 3;  // ... or it runs identity sets
   EXPECT(in, fused, 1);
-  in.pod_words = 0;
+  in.opt.pod_words = 0;
   EXPECT(in, fused, 0);
-  in.pod_rows = 1;
+  in.opt.pod_rows = 1;
   EXPECT(in, fused, 1);
 }
 
@@ -230,21 +230,21 @@ static void inplace() {
   EXPECT(in, inplace, 1);
   in.n_act[1] = 499;
   EXPECT(in, inplace, 0);
-  in.class_inplace = 1;
+  in.opt.class_inplace = 1;
   EXPECT(in, inplace, 1);
-  in.class_inplace = 0, in.n_act[1] = 8000;
+  in.opt.class_inplace = 0, in.n_act[1] = 8000;
   EXPECT(in, inplace, 0);
-  in.class_inplace = -1;
+  in.opt.class_inplace = -1;
   EXPECT(in, inplace, 1);
   in.blocks = true;
   EXPECT(in, inplace, 0);
-  in.blocks = false, in.front_fused = 0;
+  in.blocks = false, in.opt.front_fused = 0;
   EXPECT(in, inplace, 0);
   in = ido_base();  // identity sets: always, however few identities
   in.rows[0] = in.rows[1] = 1 << 20;
   in.n_act[0] = in.n_act[1] = 1;
   EXPECT(in, inplace, 1);
-  in.class_inplace = 0;
+  in.opt.class_inplace = 0;
   EXPECT(in, inplace, 0);
 }
 
@@ -260,31 +260,31 @@ static void phases_and_interleave() {
   in.P = (1 << 30) - 1, in.K = 1, in.W = in.win_wa = 1, in.rows[0] = in.rows[1] = in.P;  // 8 GiB - 8
   EXPECT(in, phase_split, 0);
   EXPECT(in, emit_interleave, 0);
-  in.emit_interleave = 1;
+  in.opt.emit_interleave = 1;
   EXPECT(in, emit_interleave, 1);
-  in.row_phases = 2;
+  in.opt.row_phases = 2;
   EXPECT(in, phase_split, ((1u << 30) - 1) / 2);
   in = ido_base();
   in.P = 1 << 15, in.K = 64, in.W = in.win_wa = 512, in.rows[0] = in.rows[1] = in.P;
-  in.emit_interleave = 0;
+  in.opt.emit_interleave = 0;
   EXPECT(in, emit_interleave, 0);
-  in.row_phases = 1;
+  in.opt.row_phases = 1;
   EXPECT(in, phase_split, 0);
-  in.row_phases = -1, in.may_err = true;
+  in.opt.row_phases = -1, in.may_err = true;
   EXPECT(in, phase_split, 0);
   in.may_err = false, in.blocks = true;
   EXPECT(in, phase_split, 0);
   in.blocks = false, in.whole = false, in.rows[0] = in.rows[1] = in.P / 2;  // a row range
   EXPECT(in, phase_split, 0);
   EXPECT(in, emit_interleave, 0);  // (its planes are 4 GiB)
-  in.row_phases = 2;
+  in.opt.row_phases = 2;
   EXPECT(in, phase_split, 0);
   in.whole = true, in.src = true, in.rows[0] = in.rows[1] = in.P;  // every source: the full window
   EXPECT(in, phase_split, 1 << 14);
   in.win_wa = 511;  // (cannot happen with every source; the rule reads the window)
   EXPECT(in, phase_split, 0);
   in = ido_base();
-  in.row_phases = 2, in.P = 128, in.rows[0] = in.rows[1] = 128;
+  in.opt.row_phases = 2, in.P = 128, in.rows[0] = in.rows[1] = 128;
   EXPECT(in, phase_split, 64);
   in.P = 127, in.rows[0] = in.rows[1] = 127;
   EXPECT(in, phase_split, 0);
@@ -295,7 +295,7 @@ static void launch() {
     for (int may_err = 0; may_err < 2 - fused; may_err++)  // (a build that may panic is never fused)
       for (int g = -1; g <= 2; g++) {
         RouteIn in = pm_base();
-        in.front_fused = fused, in.may_err = may_err != 0, in.use_graphs = g;
+        in.opt.front_fused = fused, in.may_err = may_err != 0, in.opt.graphs = g;
         const int want = g >= 0 ? g : fused ? 2 : 1;
         EXPECT(in, fused, fused);
         EXPECT(in, launch, want);

@@ -200,3 +200,64 @@ def test_comm_entry_points_validate_arguments():
     assert L.cyc_rows_merge_sources(e._ctx, None, 2, None, p) == _lib.ERR_ARG
     assert L.cyc_comm_destroy(e._ctx) == _lib.OK  # no communicator: nothing to do
     assert L.cyc_abi_version() == _lib.ABI_VERSION
+
+
+# every settable option: (default, lo, hi)
+OPTIONS = {
+    "graphs": (-1, -1, 2), "front_fused": (1, 0, 1), "pod_rows": (-1, -1, 1), "ip_range": (-1, -1, 1),
+    "ip_iv": (-1, -1, 1), "member_wave": (-1, -1, 1), "class_rpb": (0, 0, 64), "pl_wave": (1, 0, 1),
+    "sel_lazy": (-1, -1, 1), "pr_group": (-1, -1, 64), "class_inplace": (-1, -1, 1), "step_events": (0, 0, 1),
+    "emit_interleave": (-1, -1, 1), "row_phases": (-1, -1, 2), "ip_items": (-1, -1, 1), "plvt_max_mb": (1024, 0, 1 << 20),
+    "pod_words": (None, -1, 1),  # (its get reports the mode in effect and needs a prepare)
+}
+
+
+def test_option_table():
+    """cyc_set_option / cyc_get_option on a context without a GPU: every option's default, its bounds and
+    their message, the special cases (pr_group 0, row_phases' values, read-only and unknown names) and
+    what the names that need a prepare or a run answer before one."""
+    import pytest
+
+    from cyclonus_amd._lib import CyclonusError
+    from cyclonus_amd.engine import Engine
+
+    e = Engine(0)
+
+    def fails(msg, f, *a):
+        with pytest.raises(CyclonusError) as ei:
+            f(*a)
+        assert ei.value.code == _lib.ERR_ARG and ei.value.msg == msg, (a, ei.value.msg)
+
+    for name, (default, lo, hi) in OPTIONS.items():
+        if default is not None:
+            assert e.get_option(name) == default, name
+    # unprepared reads, options at their defaults
+    fails("pod_words: call cyc_probe_prepare first", e.get_option, "pod_words")
+    fails("pl_wave_active: call cyc_probe_prepare first", e.get_option, "pl_wave_active")
+    fails("class_inplace_active: run a probe first", e.get_option, "class_inplace_active")
+    assert e.get_option("launch") == 1
+    for name in ("front_fused_active", "plvt_active", "ip_iv_rows", "row_phases_active"):
+        assert e.get_option(name) == 0, name
+    for name, (default, lo, hi) in OPTIONS.items():
+        bounds = f"{name} must be in {lo}..{4 if name == 'row_phases' else hi}"
+        for v in (lo, hi):
+            e.set_option(name, v)
+            if default is not None:
+                assert e.get_option(name) == v, (name, v)
+                fails(bounds, e.set_option, name, lo - 1)
+                if name != "row_phases":
+                    fails(bounds, e.set_option, name, hi + 1)
+                assert e.get_option(name) == v, (name, v)
+        if default is None:
+            fails(bounds, e.set_option, name, lo - 1)
+            fails(bounds, e.set_option, name, hi + 1)
+    e.set_option("pr_group", 0)
+    assert e.get_option("pr_group") == -1
+    e.set_option("row_phases", 1)
+    for v in (0, 3, 4):
+        fails("row_phases must be -1 (auto), 1 (off) or 2", e.set_option, "row_phases", v)
+    fails("row_phases must be in -1..4", e.set_option, "row_phases", 5)
+    assert e.get_option("row_phases") == 1
+    fails("unknown option launch", e.set_option, "launch", 1)
+    fails("unknown option bogus", e.set_option, "bogus", 0)
+    fails("unknown option bogus", e.get_option, "bogus")

@@ -1188,3 +1188,77 @@ def test_uniform_descriptors_ido(gpu, seed):
         eng.set_option("front_fused", fused)
         assert eng.get_option("pod_words") == pod_words
         assert_same(want, eng.run_host(), f"seed {seed} pod_words {pod_words} fused {fused}")
+
+
+def test_one_context_across_problems_and_plans(gpu):
+    """One context through two problems and several range plans: every run equals the oracle's rows for
+    its range and a fresh engine's run, and a prepare leaves nothing of the previous problem's range plan
+    or last run behind.  A: 180 deployment-style pods (3 pod words), cannot panic, identity-set route;
+    B: 70 pods, panics (so it takes the PM route, eagerly)."""
+    pols_a, res_a, probes_a = _deployment_problem(14)
+    res_a = dict(res_a, Pods=res_a["Pods"][:180])
+    pols_b, res_b, probes_b = random_problem(10_006, n_pods=70, bad=True)
+    want_a = Oracle(pols_a, res_a).probe(probes_a)
+    with pytest.raises(OraclePanic) as ei:
+        Oracle(pols_b, res_b).probe(probes_b)
+    want_b = Panicked(str(ei.value))
+
+    def load(e, pols, res, probes):
+        e.build_policies(pols).load_resources(res)
+        return e.prepare(probes)
+
+    def run(e, lo=0, hi=None, part="target"):
+        try:
+            return e.run_host(lo, hi, part)
+        except CyclonusPanic as p:
+            return Panicked(p.msg)
+
+    def rows(want, lo, hi, part):
+        if isinstance(want, Panicked):
+            return want
+        st, ing, eg = want
+        if part == "source":
+            return st, ing[:, :, lo // 64:(hi + 63) // 64], eg[lo:hi]
+        return st, ing[lo:hi], eg[lo:hi]
+
+    eng = Engine(0)
+    opts = {}
+
+    def check(problem, want, ctx, lo=0, hi=None, part="target"):
+        hi = len(problem[1]["Pods"]) if hi is None else hi
+        got = run(eng, lo, hi, part)
+        assert_same(rows(want, lo, hi, part), got, ctx + ": oracle")
+        fresh = Engine(0)
+        load(fresh, *problem)
+        for k, v in opts.items():
+            fresh.set_option(k, v)
+        assert_same(run(fresh, lo, hi, part), got, ctx + ": fresh engine")
+
+    A, B = (pols_a, res_a, probes_a), (pols_b, res_b, probes_b)
+    assert load(eng, *A)["words"] == 3
+    assert eng.get_option("pod_words") == 1
+    check(A, want_a, "A whole")
+    check(A, want_a, "A sources [64, 128)", 64, 128, "source")
+    check(A, want_a, "A targets [10, 150)", 10, 150)
+    check(A, want_a, "A whole again")
+    opts = {"ip_iv": 0, "row_phases": 2}
+    for k, v in opts.items():
+        eng.set_option(k, v)
+    check(A, want_a, "A whole, ip_iv 0 row_phases 2")
+    assert eng.get_option("row_phases_active") == 2
+    load(eng, *B)
+    assert eng.get_option("pod_words") == 0  # B may panic: no identity sets
+    with pytest.raises(CyclonusError, match="class_inplace_active: run a probe first"):
+        eng.get_option("class_inplace_active")
+    fresh = Engine(0)
+    load(fresh, *B)
+    assert eng.get_option("launch") == fresh.get_option("launch")
+    with pytest.raises(CyclonusError, match="no run yet"):  # (before this change: the previous problem's last emit)
+        eng.last_emit()
+    check(B, want_b, "B whole")
+    opts = {"ip_iv": -1, "row_phases": -1}
+    for k, v in opts.items():
+        eng.set_option(k, v)
+    assert load(eng, *A)["pods"] == 180
+    assert eng.get_option("pod_words") == 1
+    check(A, want_a, "A again")
