@@ -331,11 +331,20 @@ const char* cyc_block_error(const cyc_ctx* c, int64_t b) {
   return c->run.last.blk_msg[size_t(b)].c_str();
 }
 
+// The plane pointer contract (include/cyclonus_hip.h): 64-bit words, so 8-byte aligned.  The message
+// naming the argument that is not, or null.  Checked on the host before anything is enqueued.
+static const char* misaligned_plane(const uint64_t* d_in, const uint64_t* d_eg) {
+  if (reinterpret_cast<uintptr_t>(d_in) % 8) return "d_ingress is not 8-byte aligned";
+  if (reinterpret_cast<uintptr_t>(d_eg) % 8) return "d_egress is not 8-byte aligned";
+  return nullptr;
+}
+
 int cyc_probe_run_rows(cyc_ctx* c, void* stream, uint64_t* d_in, uint64_t* d_eg, uint8_t* d_status, int part, int64_t lo,
                        int64_t hi) {
   if (!c) return CYC_ERR_ARG;
   if (!c->prepared) return fail(c, CYC_ERR_ARG, "cyc_probe_prepare first");
   if ((!d_in || !d_eg) && hi > lo) return fail(c, CYC_ERR_ARG, "null output plane");
+  if (const char* why = misaligned_plane(d_in, d_eg)) return fail(c, CYC_ERR_ARG, why);
   if (part != CYC_ROWS_TARGET && part != CYC_ROWS_SOURCE) return fail(c, CYC_ERR_ARG, "unknown partition");
   if (!c->pb.blocks.empty()) return fail(c, CYC_ERR_ARG, "context prepared for blocks: use cyc_probe_run_blocks");
   return guarded(c, [&] {
@@ -465,6 +474,7 @@ int cyc_table_wrap_rows(cyc_ctx* c, const uint64_t* d_in, const uint64_t* d_eg, 
   *out = nullptr;
   if (!c->prepared) return fail(c, CYC_ERR_ARG, "cyc_probe_prepare first");
   if (!d_status || ((!d_in || !d_eg) && hi > lo)) return fail(c, CYC_ERR_ARG, "null plane");
+  if (const char* why = misaligned_plane(d_in, d_eg)) return fail(c, CYC_ERR_ARG, why);
   cyc_table* t = nullptr;
   int rc = table_new(c, part, lo, hi, &t);
   if (rc != CYC_OK) return rc;
@@ -664,6 +674,9 @@ int cyc_get_option(cyc_ctx* c, const char* name, int64_t* value) {
   } else if (n == "class_inplace_active") {
     if (!c->prepared || !c->range.valid) return fail(c, CYC_ERR_ARG, "class_inplace_active: run a probe first");
     *value = c->route.inplace ? 1 : 0;
+  } else if (n == "emit_interleave_active") {
+    if (!c->prepared || !c->range.valid) return fail(c, CYC_ERR_ARG, "emit_interleave_active: run a probe first");
+    *value = c->route.emit_interleave ? 1 : 0;
   } else if (n == "plvt_active") *value = c->prep.plvt_ready ? 1 : 0;
   else if (n == "ip_iv_rows") *value = c->range.Rv;  // (the last range plan's interval-built rows)
   else if (n == "row_phases_active") *value = c->run.last.phase_used;  // (the last run's phases; 0: a plain run)

@@ -318,7 +318,7 @@ static const char* enq_emit_launch(const EmitArgs& ea_in, hipStream_t st, uint64
   if (row_bytes > 512 * 7 * 16 && row_bytes <= 1024 * 7 * 16) {
     k_emit_wide_buf<1024, 7><<<g, 1024, 0, st>>>(ea);
     return "k_emit_wide_buf<1024,7>";
-  } else if (row_bytes > 512 * 7 * 16) {  // > 104 KB: 1024 x 7 passes
+  } else if (row_bytes > 512 * 7 * 16) {  // > 112 KB (114,688 B): 1024 x 7 passes
     k_emit_wide<1024, 7><<<g, 1024, 0, st>>>(ea);
     return "k_emit_wide<1024,7>";
   } else if (row_bytes > 256 * 8 * 16) {  // 32-56 KB: 512 x 7 (source shards at N = 2)
@@ -327,13 +327,12 @@ static const char* enq_emit_launch(const EmitArgs& ea_in, hipStream_t st, uint64
   } else if (row_bytes >= EMIT_WIDE_MIN) {  // 256-thread single pass (16-32 KB rows; buffer-op 256 x 8,
                                             // 512 x 4 and 1024 x 2 blocks were no better over 4 plane
                                             // placements of config #4, profiles/r05_plane_placement.txt)
-    const uint64_t need = (ea.row_words / 2 + 255) / 256;
-    if (need <= 2) k_emit_wide<256, 2><<<g, 256, 0, st>>>(ea);
-    else if (need <= 4) k_emit_wide<256, 4><<<g, 256, 0, st>>>(ea);
+    const uint64_t need = (ea.row_words / 2 + 255) / 256;  // 4 (EMIT_WIDE_MIN) to 8
+    if (need <= 4) k_emit_wide<256, 4><<<g, 256, 0, st>>>(ea);
     else if (need <= 6) k_emit_wide<256, 6><<<g, 256, 0, st>>>(ea);
     else if (need <= 7) k_emit_wide<256, 7><<<g, 256, 0, st>>>(ea);
     else k_emit_wide<256, 8><<<g, 256, 0, st>>>(ea);
-    return need <= 2 ? "k_emit_wide<256,2>" : need <= 4 ? "k_emit_wide<256,4>" : need <= 6 ? "k_emit_wide<256,6>"
+    return need <= 4 ? "k_emit_wide<256,4>" : need <= 6 ? "k_emit_wide<256,6>"
          : need <= 7 ? "k_emit_wide<256,7>" : "k_emit_wide<256,8>";
   } else {  // flat multi-row sweep over ~32 KB per block
     ea.chunk = uint32_t(std::min<uint64_t>(EMIT_FLAT_MAX_ROWS, std::max<uint64_t>(1, 32768 / row_bytes)));

@@ -219,7 +219,14 @@ int64_t cyc_resources_json(cyc_ctx* ctx, char* buf, size_t cap);
  * unless the inputs can panic (then it synchronises to report the first panicking job in job
  * order, as the reference would).  The planes must be device memory (hipMalloc and the like), read
  * back by hipMemcpy or by kernels after the stream: the run's events release at device scope, so
- * host-mapped, non-coherent memory is not made visible to the host by a stream synchronisation. */
+ * host-mapped, non-coherent memory is not made visible to the host by a stream synchronisation.
+ * Alignment: d_ingress and d_egress are planes of 64-bit words and must be 8-byte aligned; a pointer
+ * that is not is refused with CYC_ERR_ARG (the message names the argument) before anything is
+ * enqueued, here and in cyc_probe_run_rows, cyc_table_wrap and cyc_table_wrap_rows.  16-byte aligned
+ * planes (hipMalloc's are) enable the vector paths: the 16-byte emit kernels (when the plane rows are
+ * an even number of words too) and the class rows' 16-byte pair stores; 8-byte aligned planes get the
+ * same bits through 8-byte stores (cyc_last_emit then names k_emit_words).  d_status has no
+ * alignment requirement.  The library writes exactly the planes' bytes, nothing before or after. */
 int cyc_probe_run(cyc_ctx* ctx, void* hip_stream, uint64_t* d_ingress, uint64_t* d_egress, uint8_t* d_status,
                   int64_t row_lo, int64_t row_hi);
 
@@ -248,6 +255,7 @@ typedef enum { CYC_ROWS_TARGET = 0, CYC_ROWS_SOURCE = 1 } cyc_rows;
  * ingress (row, slot), out[2] egress rows, out[3] words per egress (row, slot), out[4] the ingress
  * window's first word (0 for target rows).  Needs cyc_probe_prepare. */
 int cyc_rows_layout(cyc_ctx* ctx, int partition, int64_t row_lo, int64_t row_hi, int64_t* out, int n);
+/* cyc_probe_run under a partition.  Plane alignment: as cyc_probe_run (8-byte aligned planes, or CYC_ERR_ARG). */
 int cyc_probe_run_rows(cyc_ctx* ctx, void* hip_stream, uint64_t* d_ingress, uint64_t* d_egress, uint8_t* d_status,
                        int partition, int64_t row_lo, int64_t row_hi);
 int cyc_probe_run_host_rows(cyc_ctx* ctx, uint64_t* ingress, uint64_t* egress, uint8_t* status, int partition,
@@ -275,10 +283,12 @@ typedef struct cyc_table cyc_table;
  * are reported as by cyc_probe_run).  A table stays valid after its context is destroyed. */
 int cyc_table_run(cyc_ctx* ctx, int64_t row_lo, int64_t row_hi, cyc_table** out);
 /* A table over planes the caller produced with cyc_probe_run (device pointers, not owned; they
- * must outlive the table and the run must be complete before cyc_table_cells). */
+ * must outlive the table and the run must be complete before cyc_table_cells).  Plane alignment: as
+ * cyc_probe_run (8-byte aligned planes, or CYC_ERR_ARG). */
 int cyc_table_wrap(cyc_ctx* ctx, const uint64_t* d_ingress, const uint64_t* d_egress, const uint8_t* d_status,
                    int64_t row_lo, int64_t row_hi, cyc_table** out);
-/* The same under a row partition (cyc_probe_run_rows).  A CYC_ROWS_SOURCE table answers every cell
+/* The same under a row partition (cyc_probe_run_rows; cyc_table_wrap_rows: plane alignment as
+ * cyc_probe_run).  A CYC_ROWS_SOURCE table answers every cell
  * (s, d, k) with s inside its rows: Ingress, Egress and Combined of Table.Get(from = s, to = d). */
 int cyc_table_run_rows(cyc_ctx* ctx, int partition, int64_t row_lo, int64_t row_hi, cyc_table** out);
 int cyc_table_wrap_rows(cyc_ctx* ctx, const uint64_t* d_ingress, const uint64_t* d_egress, const uint8_t* d_status,
@@ -425,7 +435,8 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  *                 rows build on the device; beyond it (0: always) they gather through each pod's label set
  * cyc_get_option also reports "launch" (the graphs mode in effect), "row_phases_active" (the last
  * run's phases: 2, or 0), "front_fused_active", "pl_wave_active" (needs cyc_probe_prepare),
- * "class_inplace_active" (needs a run), "plvt_active" and "ip_iv_rows" (the current range plan's
+ * "class_inplace_active" and "emit_interleave_active" (the routes in effect; they need a run),
+ * "plvt_active" and "ip_iv_rows" (the current range plan's
  * interval-built IP rows); "pod_words" reports the mode the prepared probe uses (0 or 1; needs
  * cyc_probe_prepare). */
 int cyc_set_option(cyc_ctx* ctx, const char* name, int64_t value);
