@@ -127,12 +127,24 @@ constexpr uint32_t PB_HALF_MAX = 4;
 #endif
 // Identity words [ew0, ew0 + new) of the rows only (a source shard's ingress peers: the words of the
 // egress identities its sources have).
-__device__ __forceinline__ void peer_bits_blk(uint32_t Rp, uint32_t E, uint32_t EW, const uint32_t* __restrict__ pod_peers,
-                                                   const DPeer* __restrict__ peers, const SelView& sv,
-                                                   const uint32_t* __restrict__ id_ns, const uint32_t* __restrict__ id_nsls,
-                                                   const uint32_t* __restrict__ id_ls, uint64_t* __restrict__ idob, uint32_t bid_, uint32_t nblk_,
-                                                   uint32_t ew0, uint32_t new_, const uint2* __restrict__ grp_ns,
-                                                   const uint2* __restrict__ word_ns, const uint4* __restrict__ prec = nullptr) {
+struct IdentArgs {
+  uint32_t nb, Ru;             // the direction's distinct pod-peer matchers
+  const uint32_t* pod_peers;
+  uint64_t* idob;
+  uint32_t ew0, new_;
+  const uint2 *grp_ns, *word_ns;  // namespace ranges per group of PB_GROUP rows, per egress identity word
+  const uint4* pbrec;          // per row its matcher records (pb_rec; null: the peers' chains)
+};
+// LAZY false (the stand-alone kernel: the two-branch DAG always builds the dense selector table): only
+// the table gathers are compiled.
+template <bool LAZY = true>
+__device__ __forceinline__ void peer_bits_blk(const PeerCommon& c, const IdentArgs& a, uint32_t bid_) {
+  const uint32_t Rp = a.Ru, E = c.E, EW = c.EW, ew0 = a.ew0, new_ = a.new_;
+  const SelView& sv = c.sv;
+  const uint32_t* pod_peers = a.pod_peers;
+  const DPeer* peers = c.peers;
+  uint64_t* idob = a.idob;
+  const uint4* prec = a.pbrec;
   // the wave index is wave-uniform: a scalar, so the peers' records below are scalar loads
   const uint32_t wv = __builtin_amdgcn_readfirstlane(bid_ * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const uint32_t groups = (Rp + PB_GROUP - 1) / PB_GROUP;
@@ -142,12 +154,12 @@ __device__ __forceinline__ void peer_bits_blk(uint32_t Rp, uint32_t E, uint32_t 
   // part, ONE vector load — are issued before the skip test's loads, so their latencies overlap
   const uint32_t e = ew * 64 + lane;
   const bool live = e < E;
-  const uint32_t ns = live ? id_ns[e] : 0u, nsls = live ? id_nsls[e] : 0u, ls = live ? id_ls[e] : 0u;
-  const bool use_rec = prec && !sv.selres;
+  const uint32_t ns = live ? c.id_ns[e] : 0u, nsls = live ? c.id_nsls[e] : 0u, ls = live ? c.id_ls[e] : 0u;
+  const bool use_rec = LAZY && prec && !sv.selres;
   const uint4 R = use_rec ? prec[min(3 * g0 + (lane < 3 * PB_GROUP ? lane : 0u), 3 * Rp - 1)] : uint4{0, 0, 0, 0};
   {  // a group of exact-namespace peers (podpeermatcher.go:115-125: ns == the policy's namespace) whose
      // namespaces the word's identities do not have matches none of them: zeros, no selector loads
-    const uint2 gr = grp_ns[g], wr = word_ns[ew];
+    const uint2 gr = a.grp_ns[g], wr = a.word_ns[ew];
     if (gr.y < wr.x || gr.x > wr.y) {
       const uint32_t p = g0 + lane;
       if (lane < PB_GROUP && p < Rp) idob[uint64_t(p) * EW + ew] = 0;
@@ -210,7 +222,7 @@ __device__ __forceinline__ void peer_bits_blk(uint32_t Rp, uint32_t E, uint32_t 
       ps[x] = pr.podsel;
     }
     uint32_t rn[PB_HALF], rp[PB_HALF];
-    if (sv.selres) {  // dense selector table: one byte gather per matcher, all issued unconditionally
+    if (!LAZY || sv.selres) {  // dense selector table: one byte gather per matcher, all issued unconditionally
       uint8_t an[PB_HALF], ap[PB_HALF];
 #pragma unroll
       for (uint32_t x = 0; x < PB_HALF; x++) an[x] = sv.selres[uint64_t(nk[x] == 2 ? nv[x] : 0u) * sv.L + nsls];
@@ -254,16 +266,7 @@ __device__ __forceinline__ void peer_bits_blk(uint32_t Rp, uint32_t E, uint32_t 
   const uint32_t p = g * PB_GROUP + lane;
   if (lane < PB_GROUP && p < Rp) idob[uint64_t(p) * EW + ew] = mine;
 }
-__global__ __launch_bounds__(256) void k_peer_bits(uint32_t Rp, uint32_t E, uint32_t EW, const uint32_t* __restrict__ pod_peers,
-                                                   const DPeer* __restrict__ peers, const uint8_t* __restrict__ selres, uint32_t L,
-                                                   const uint32_t* __restrict__ id_ns, const uint32_t* __restrict__ id_nsls,
-                                                   const uint32_t* __restrict__ id_ls, uint64_t* __restrict__ idob, uint32_t ew0,
-                                                   uint32_t new_, const uint2* __restrict__ grp_ns, const uint2* __restrict__ word_ns) {
-  SelView sv{};
-  sv.selres = selres;
-  sv.L = L;
-  peer_bits_blk(Rp, E, EW, pod_peers, peers, sv, id_ns, id_nsls, id_ls, idob, blockIdx.x, gridDim.x, ew0, new_, grp_ns, word_ns);
-}
+__global__ __launch_bounds__(256) void k_peer_bits(PeerCommon c, IdentArgs a) { peer_bits_blk<false>(c, a, blockIdx.x); }
 
 // Per class representative and NB index (ingress: job slot, egress: job descriptor): the set of
 // egress identities its targets' pod / all / ports-for-all peers allow on that port (target.go:29-36

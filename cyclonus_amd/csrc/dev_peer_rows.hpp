@@ -5,42 +5,63 @@
 
 namespace cyc {
 
+// What the peer-row stages share (peer_common): held once per launch, next to each segment's own struct.
+struct PeerCommon {
+  uint32_t P, W, E, EW;  // pods, words of a row, egress identities and their words
+  uint64_t *PM, *ER;     // (ER: builds that can panic only)
+  uint32_t *rng, *cnz;   // per peer row: word span and chunk masks; nonzero-chunk flags (ip_row_word)
+  const DPeer* peers;
+  SelView sv;            // selector outcomes (SELRES or evaluated where used)
+  const uint32_t *id_ns, *id_nsls, *id_ls;  // egress identities
+  const uint32_t* pod_eid;                   // pod -> egress identity
+  const uint32_t *pod_ns, *pod_nsls, *pod_ls;
+  const struct DWordNS* nsw;  // per word, then per chunk: namespace ranges
+  const struct DWordIP* words;
+  const DIP* pod_ip;
+  const DCidr* ip_ex;
+  const uint4* req_post;      // label postings (pod_rows_post_blk)
+  const uint32_t* post_pods;
+};
+
 // Pod peers depend on a peer pod only through its (namespace, labels) identity, so they are
-// evaluated once per (pod peer, egress identity) -> IDO u8 [Rpod][E] ...
-__global__ void k_peer_ident(uint32_t Rp, uint32_t E, const uint32_t* __restrict__ pod_peers, const DPeer* __restrict__ peers,
-                             const uint8_t* __restrict__ selres, uint32_t L, const uint32_t* __restrict__ id_ns,
-                             const uint32_t* __restrict__ id_nsls, const uint32_t* __restrict__ id_ls,
-                             uint8_t* __restrict__ ido) {
-  uint64_t n = uint64_t(Rp) * E;
+// evaluated once per (pod peer, egress identity) -> IDO u8 [Rpod][E] (the dense selector table only:
+// builds that can panic, or whose pod-peer rows the fused front does not take) ...
+struct PodRunsArgs {
+  uint32_t nb_ident, nb, Rp;
+  const uint32_t* pod_peers;
+  uint8_t* ido;
+  const uint32_t *word_off, *run_e;
+  const uint64_t* run_mask;
+  uint32_t w0, nw;
+};
+__global__ void k_peer_ident(PeerCommon c, PodRunsArgs a) {
+  uint64_t n = uint64_t(a.Rp) * c.E;
   for (uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
-    uint32_t p = uint32_t(i / E), e = uint32_t(i % E);
-    DPeer pr = peers[pod_peers[p]];
-    ido[i] = uint8_t(pod_peer_outcome(pr, selres, L, id_ns[e], id_nsls[e], id_ls[e]));
+    uint32_t p = uint32_t(i / c.E), e = uint32_t(i % c.E);
+    DPeer pr = c.peers[a.pod_peers[p]];
+    a.ido[i] = uint8_t(pod_peer_outcome(pr, c.sv.selres, c.sv.L, c.id_ns[e], c.id_nsls[e], c.id_ls[e]));
   }
 }
 
 // ... then expanded to packed pod rows through each 64-pod word's identity runs (word_off /
 // run_e / run_mask; pods of one identity are usually contiguous, so a word holds 1-2 runs).
 template <bool ERR>
-__global__ __launch_bounds__(256) void k_pod_rows(uint32_t Rp, uint32_t E, uint32_t W, const uint32_t* __restrict__ pod_peers,
-                                                  const uint8_t* __restrict__ ido, const uint32_t* __restrict__ word_off,
-                                                  const uint32_t* __restrict__ run_e, const uint64_t* __restrict__ run_mask,
-                                                  uint64_t* __restrict__ PM, uint64_t* __restrict__ ER, uint32_t w0, uint32_t nw) {
-  uint32_t chunks = (nw + 255) / 256;
+__global__ __launch_bounds__(256) void k_pod_rows(PeerCommon c, PodRunsArgs a) {
+  uint32_t chunks = (a.nw + 255) / 256;
   uint32_t p = blockIdx.x / chunks;
-  uint32_t w = w0 + (blockIdx.x % chunks) * 256 + threadIdx.x;
-  if (p >= Rp || w >= w0 + nw) return;
-  const uint8_t* row = ido + uint64_t(p) * E;
+  uint32_t w = a.w0 + (blockIdx.x % chunks) * 256 + threadIdx.x;
+  if (p >= a.Rp || w >= a.w0 + a.nw) return;
+  const uint8_t* row = a.ido + uint64_t(p) * c.E;
   uint64_t m = 0, e = 0;
-  for (uint32_t x = word_off[w]; x < word_off[w + 1]; x++) {
-    uint8_t o = row[run_e[x]];
-    uint64_t mk = run_mask[x];
+  for (uint32_t x = a.word_off[w]; x < a.word_off[w + 1]; x++) {
+    uint8_t o = row[a.run_e[x]];
+    uint64_t mk = a.run_mask[x];
     m |= o == 1 ? mk : 0ull;
     if (ERR) e |= o == 2 ? mk : 0ull;
   }
-  uint64_t j = pod_peers[p];
-  PM[j * W + w] = m;
-  if (ERR) ER[j * W + w] = e;
+  uint64_t j = a.pod_peers[p];
+  c.PM[j * c.W + w] = m;
+  if (ERR) c.ER[j * c.W + w] = e;
 }
 
 struct DWordNS {
@@ -58,9 +79,6 @@ constexpr uint32_t PR_DIRECT_G = 4;  // pod peers per wave of the direct pod-pee
 // Wave = (PR_DIRECT_G pod peers, one 64-pod word), lane = pod: the word's pod identities (pod ->
 // identity -> namespace, namespace labels, labels) are loaded once for the group, then every
 // peer's two matcher bytes at once, one ballot per peer.
-__host__ __device__ inline uint64_t pod_direct_waves(uint32_t Rp, uint32_t nw) {
-  return uint64_t((Rp + PR_DIRECT_G - 1) / PR_DIRECT_G) * nw;
-}
 // No panic possible (the fused front): both matchers through a SelView — the dense selector table, or
 // selectors evaluated here (one-requirement records: one label-table gather each) when the front builds
 // no table (sel_lazy), so a PM build with full pod-peer rows needs no launch A.
@@ -71,15 +89,15 @@ __device__ __forceinline__ uint32_t pod_peer_match_sv(const DPeer& pr, const Sel
   if (pr.nskind == 0) return ns == pr.nsval && rp == 1 ? 1u : 0u;
   return rn == 1 && rp == 1 ? 1u : 0u;
 }
-template <bool ERR>
-__device__ __forceinline__ void pod_rows_direct_blk(uint32_t Rp, uint32_t P, uint32_t W,
-                                                         const uint32_t* __restrict__ pod_peers,
-                                                         const DPeer* __restrict__ peers, const SelView& sv,
-                                                         const uint32_t* __restrict__ pod_eid,
-                                                         const uint32_t* __restrict__ id_ns, const uint32_t* __restrict__ id_nsls,
-                                                         const uint32_t* __restrict__ id_ls, uint64_t* __restrict__ PM,
-                                                         uint64_t* __restrict__ ER, uint32_t bid_, uint32_t nblk_, uint32_t w0,
-                                                         uint32_t nw) {
+struct PodDirectArgs {
+  uint32_t nb, Rp;
+  const uint32_t* pod_peers;
+  uint32_t w0, nw;
+};
+template <bool ERR, bool LAZY>  // LAZY false (the stand-alone kernels): only the dense-table gathers are compiled
+__device__ __forceinline__ void pod_rows_direct_blk(const PeerCommon& c, const PodDirectArgs& a, uint32_t bid_) {
+  const uint32_t Rp = a.Rp, P = c.P, W = c.W, w0 = a.w0, nw = a.nw;
+  const SelView& sv = c.sv;
   const uint32_t lane = threadIdx.x & 63, gw = __builtin_amdgcn_readfirstlane(bid_ * 4 + (threadIdx.x >> 6));  // wave-uniform
   const uint32_t g = gw / nw, w = w0 + (gw - g * nw), p0 = g * PR_DIRECT_G;
   if (p0 >= Rp) return;
@@ -87,16 +105,16 @@ __device__ __forceinline__ void pod_rows_direct_blk(uint32_t Rp, uint32_t P, uin
   DPeer pr[PR_DIRECT_G];
 #pragma unroll
   for (uint32_t u = 0; u < PR_DIRECT_G; u++) {
-    j[u] = pod_peers[min(p0 + u, Rp - 1)];
-    pr[u] = peers[j[u]];
+    j[u] = a.pod_peers[min(p0 + u, Rp - 1)];
+    pr[u] = c.peers[j[u]];
   }
   const uint32_t q = w * 64 + lane;
-  const uint32_t e = pod_eid[min(q, P - 1)];  // (clamped: no load inside a branch)
-  const uint32_t ns = id_ns[e], nsls = id_nsls[e], ls = id_ls[e];
+  const uint32_t e = c.pod_eid[min(q, P - 1)];  // (clamped: no load inside a branch)
+  const uint32_t ns = c.id_ns[e], nsls = c.id_nsls[e], ls = c.id_ls[e];
   uint32_t o[PR_DIRECT_G];
 #pragma unroll
   for (uint32_t u = 0; u < PR_DIRECT_G; u++)
-    o[u] = ERR || sv.selres ? pod_peer_outcome(pr[u], sv.selres, sv.L, ns, nsls, ls) : pod_peer_match_sv(pr[u], sv, ns, nsls, ls);
+    o[u] = !LAZY || sv.selres ? pod_peer_outcome(pr[u], sv.selres, sv.L, ns, nsls, ls) : pod_peer_match_sv(pr[u], sv, ns, nsls, ls);
 #pragma unroll
   for (uint32_t u = 0; u < PR_DIRECT_G; u++) {
     if (p0 + u >= Rp) break;  // wave-uniform
@@ -104,24 +122,13 @@ __device__ __forceinline__ void pod_rows_direct_blk(uint32_t Rp, uint32_t P, uin
     const uint64_t m = __ballot(ou == 1);
     const uint64_t er = ERR ? __ballot(ou == 2) : 0ull;
     if (lane == 0) {
-      PM[uint64_t(j[u]) * W + w] = m;
-      if (ERR) ER[uint64_t(j[u]) * W + w] = er;
+      c.PM[uint64_t(j[u]) * W + w] = m;
+      if (ERR) c.ER[uint64_t(j[u]) * W + w] = er;
     }
   }
 }
 template <bool ERR>
-__global__ __launch_bounds__(256) void k_pod_rows_direct(uint32_t Rp, uint32_t P, uint32_t W,
-                                                         const uint32_t* __restrict__ pod_peers,
-                                                         const DPeer* __restrict__ peers, const uint8_t* __restrict__ selres,
-                                                         uint32_t L, const uint32_t* __restrict__ pod_eid,
-                                                         const uint32_t* __restrict__ id_ns, const uint32_t* __restrict__ id_nsls,
-                                                         const uint32_t* __restrict__ id_ls, uint64_t* __restrict__ PM,
-                                                         uint64_t* __restrict__ ER, uint32_t w0, uint32_t nw) {
-  SelView sv{};
-  sv.selres = selres;
-  sv.L = L;
-  pod_rows_direct_blk<ERR>(Rp, P, W, pod_peers, peers, sv, pod_eid, id_ns, id_nsls, id_ls, PM, ER, blockIdx.x, gridDim.x, w0, nw);
-}
+__global__ __launch_bounds__(256) void k_pod_rows_direct(PeerCommon c, PodDirectArgs a) { pod_rows_direct_blk<ERR, false>(c, a, blockIdx.x); }
 
 // Pod-peer rows of the fused front on PM builds (no panic possible), stored sparse, 64-word chunks
 // at a time with lane = pod word (block shapes: pod_rows_sparse_blk).  The namespace
@@ -237,13 +244,15 @@ __device__ __forceinline__ void pod_chunk_store(uint32_t j, uint32_t chunk, uint
 // peers: the grid is large anyway).  grp == 1: block = (pod peer, 4 chunks) taken one chunk at a
 // time, each chunk's open words split over the 4 waves and met in LDS (few peers with dense rows:
 // config #2 26 us, where a wave per chunk leaves 3 waves per peer and takes 100 us).
-__device__ __forceinline__ void pod_rows_sparse_blk(uint32_t Rp, uint32_t P, uint32_t W, const uint32_t* __restrict__ plist,
-                                                    const DPeer* __restrict__ peers, const SelView& sv,
-                                                    const uint32_t* __restrict__ pod_ns,
-                                                    const uint32_t* __restrict__ pod_nsls, const uint32_t* __restrict__ pod_ls,
-                                                    const DWordNS* __restrict__ nsw, uint64_t* __restrict__ PM,
-                                                    uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz, uint32_t grp,
-                                                    uint32_t bid_, uint32_t c0, uint32_t nch) {
+struct PodSparseArgs {
+  uint32_t nb, nb_post;  // blocks of pod_rows_sparse_blk over plist, of pod_rows_post_blk over plist_post
+  uint32_t Rp, grp;
+  const uint32_t *plist, *plist_post;
+  uint32_t c0, nch;
+};
+__device__ __forceinline__ void pod_rows_sparse_rows(const PeerCommon& c, const PodSparseArgs& a, uint64_t* __restrict__ PM,
+                                                     uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz, uint32_t bid_) {
+  const uint32_t Rp = a.Rp, P = c.P, W = c.W, grp = a.grp, c0 = a.c0, nch = a.nch;
   __shared__ uint64_t s_m[4][64];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t chunks = (W + 63) / 64, cb = (nch + 3) / 4;  // chunks [c0, c0 + nch) of each row
@@ -252,34 +261,37 @@ __device__ __forceinline__ void pod_rows_sparse_blk(uint32_t Rp, uint32_t P, uin
   if (grp > 1) {
     const uint32_t chunk = __builtin_amdgcn_readfirstlane(c0 + (bid_ % cb) * 4 + wave);
     if (chunk >= c0 + nch) return;
-    const DWordNS ck = nsw[W + chunk];
+    const DWordNS ck = c.nsw[W + chunk];
     for (uint32_t x = x0; x < min(Rp, x0 + grp); x++) {
-      const uint32_t j = plist[x];
-      const DPeer pr = peers[j];
+      const uint32_t j = a.plist[x];
+      const DPeer pr = c.peers[j];
       if (pr.nskind == 0 && (pr.nsval < ck.lo || pr.nsval > ck.hi)) {  // no pod of the namespace here
         if (lane == 0) cnz[uint64_t(j) * chunks + chunk] = 0;
         continue;
       }
-      const uint64_t v = pod_chunk_words(pr, sv, P, W, chunk, lane, 0, 1, pod_ns, pod_nsls, pod_ls, nsw);
+      const uint64_t v = pod_chunk_words(pr, c.sv, P, W, chunk, lane, 0, 1, c.pod_ns, c.pod_nsls, c.pod_ls, c.nsw);
       pod_chunk_store(j, chunk, W, lane, v, PM, rng, cnz);
     }
     return;
   }
-  const uint32_t j = plist[x0];
-  const DPeer pr = peers[j];
+  const uint32_t j = a.plist[x0];
+  const DPeer pr = c.peers[j];
   for (uint32_t ci = 0; ci < 4; ci++) {
     const uint32_t chunk = c0 + (bid_ % cb) * 4 + ci;  // block-uniform
     if (chunk >= c0 + nch) break;
-    const DWordNS ck = nsw[W + chunk];
+    const DWordNS ck = c.nsw[W + chunk];
     if (pr.nskind == 0 && (pr.nsval < ck.lo || pr.nsval > ck.hi)) {
       if (threadIdx.x == 0) cnz[uint64_t(j) * chunks + chunk] = 0;
       continue;
     }
-    s_m[wave][lane] = pod_chunk_words(pr, sv, P, W, chunk, lane, wave, 4, pod_ns, pod_nsls, pod_ls, nsw);
+    s_m[wave][lane] = pod_chunk_words(pr, c.sv, P, W, chunk, lane, wave, 4, c.pod_ns, c.pod_nsls, c.pod_ls, c.nsw);
     __syncthreads();
     if (wave == 0) pod_chunk_store(j, chunk, W, lane, s_m[0][lane] | s_m[1][lane] | s_m[2][lane] | s_m[3][lane], PM, rng, cnz);
     __syncthreads();  // s_m is reused by the next chunk
   }
+}
+__device__ __forceinline__ void pod_rows_sparse_blk(const PeerCommon& c, const PodSparseArgs& a, uint32_t bid_) {
+  pod_rows_sparse_rows(c, a, c.PM, c.rng, c.cnz, bid_);  // (restrict parameters: ip_rows_iv_rows)
 }
 
 // IP peers depend on each pod's own address: one wave per 64-pod word (one lane per pod).  A
@@ -293,12 +305,21 @@ struct DIPTest {
   DCidr cidr;
 };
 
+// One segment of the IP rows built per word: k_ip_rows_fast's groups, the fused front's work items
+// (items non-null: ip_rows_items_blk), or the panic path's batches (k_ip_rows).
+struct IpArgs {
+  uint32_t nb, Ri;
+  const DIPTest* tests;
+  uint32_t grp, c0, nch;        // fast rows: peers per block, chunk window
+  const struct DIPItem* items;  // work items of the segment, a wave each
+  uint32_t n_items;
+  const uint32_t* ilist;
+  uint32_t batch, w0, nw;       // panic path: peers per block, word window
+};
 // Words [w0, w0 + nw) of the rows only (a source shard's ingress peers: the shard's word window).
 template <bool ERR>
-__global__ __launch_bounds__(256) void k_ip_rows(uint32_t Ri, uint32_t P, uint32_t W, const DIPTest* __restrict__ tests,
-                                                 const DCidr* __restrict__ ip_ex, const DIP* __restrict__ pod_ip,
-                                                 uint64_t* __restrict__ PM, uint64_t* __restrict__ ER, uint32_t batch,
-                                                 uint32_t w0, uint32_t nw) {
+__global__ __launch_bounds__(256) void k_ip_rows(PeerCommon c, IpArgs a) {
+  const uint32_t Ri = a.Ri, P = c.P, W = c.W, batch = a.batch, w0 = a.w0, nw = a.nw;
   __shared__ DIPTest s_t[IPB_BATCH];
   __shared__ DCidr s_ex[IPB_EX_LDS];
   const uint32_t wchunks = (nw + 3) / 4;
@@ -306,15 +327,15 @@ __global__ __launch_bounds__(256) void k_ip_rows(uint32_t Ri, uint32_t P, uint32
   const uint32_t w = w0 + (blockIdx.x % wchunks) * 4 + wave;
   const uint32_t r0 = (blockIdx.x / wchunks) * batch;
   const uint32_t nr = min(Ri - r0, batch);
-  const uint32_t ex0 = tests[r0].exoff;
-  const uint32_t nex = tests[r0 + nr - 1].exoff + tests[r0 + nr - 1].excnt - ex0;
-  for (uint32_t t = threadIdx.x; t < nr; t += blockDim.x) s_t[t] = tests[r0 + t];
-  for (uint32_t t = threadIdx.x; t < min(nex, IPB_EX_LDS); t += blockDim.x) s_ex[t] = ip_ex[ex0 + t];
+  const uint32_t ex0 = a.tests[r0].exoff;
+  const uint32_t nex = a.tests[r0 + nr - 1].exoff + a.tests[r0 + nr - 1].excnt - ex0;
+  for (uint32_t t = threadIdx.x; t < nr; t += blockDim.x) s_t[t] = a.tests[r0 + t];
+  for (uint32_t t = threadIdx.x; t < min(nex, IPB_EX_LDS); t += blockDim.x) s_ex[t] = c.ip_ex[ex0 + t];
   __syncthreads();
   if (w >= w0 + nw) return;
   const uint32_t q = w * 64 + lane;
   DIP ip{};
-  if (q < P) ip = pod_ip[q];
+  if (q < P) ip = c.pod_ip[q];
   const bool live = q < P;
   for (uint32_t r = 0; r < nr; r++) {
     const DIPTest& t = s_t[r];
@@ -326,7 +347,7 @@ __global__ __launch_bounds__(256) void k_ip_rows(uint32_t Ri, uint32_t P, uint32
       o = 1;
       for (uint32_t e = 0; e < t.excnt; e++) {
         uint32_t xi = t.exoff + e - ex0;
-        const DCidr& x = xi < IPB_EX_LDS ? s_ex[xi] : ip_ex[t.exoff + e];
+        const DCidr& x = xi < IPB_EX_LDS ? s_ex[xi] : c.ip_ex[t.exoff + e];
         if (!x.valid) {
           o = 2;
           break;
@@ -341,8 +362,8 @@ __global__ __launch_bounds__(256) void k_ip_rows(uint32_t Ri, uint32_t P, uint32
     uint64_t m = __ballot(o == 1);
     uint64_t e = ERR ? __ballot(o == 2) : 0ull;
     if (lane == 0) {
-      PM[uint64_t(t.peer) * W + w] = m;
-      if (ERR) ER[uint64_t(t.peer) * W + w] = e;
+      c.PM[uint64_t(t.peer) * W + w] = m;
+      if (ERR) c.ER[uint64_t(t.peer) * W + w] = e;
     }
   }
 }
@@ -571,26 +592,31 @@ union IpRowsLds {
   unsigned long long row[4][IPR_SPAN];
 };
 __shared__ IpRowsLds ip_lds;
-__device__ __forceinline__ void ip_rows_range_blk(uint32_t Rr, uint32_t W, const DIPRange* __restrict__ rt,
-                                                  const uint2* __restrict__ iv, const uint32_t* __restrict__ sorted,
-                                                  uint64_t* __restrict__ PM, uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz,
-                                                  uint32_t bid_, uint32_t c0, uint32_t nch) {
+struct IpRangeArgs {
+  uint32_t nb, Rr;
+  const DIPRange* rt;
+  const uint2* iv;
+  const uint32_t* sorted;
+  uint32_t c0, nch;
+};
+__device__ __forceinline__ void ip_rows_range_blk(const PeerCommon& cm, const IpRangeArgs& a, uint32_t bid_) {
+  const uint32_t W = cm.W, c0 = a.c0, nch = a.nch;
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t r = __builtin_amdgcn_readfirstlane(bid_ * 4 + wv);  // wave-uniform
   unsigned long long* row = ip_lds.row[wv];
-  const bool live = r < Rr;
+  const bool live = r < a.Rr;
   for (uint32_t x = lane; x < IPR_SPAN; x += 64) row[x] = 0;
   DIPRange t{};
-  if (live) t = rt[r];
+  if (live) t = a.rt[r];
   // the LDS window: the span's words inside the run's word window (a source shard's ingress peers)
   const uint32_t lo_w = max(t.sw0, c0 * 64), hi_w = min(min(t.sw0 + IPR_SPAN, (c0 + nch) * 64), W);
   __syncthreads();
   for (uint32_t i = 0; live && i < t.ivcnt; i++) {
-    const uint2 v = iv[t.ivoff + i];
+    const uint2 v = a.iv[t.ivoff + i];
     for (uint32_t p0 = v.x; p0 < v.y; p0 += 4 * 64) {  // 4 pods a lane in flight
       uint32_t q[4];
 #pragma unroll
-      for (uint32_t u = 0; u < 4; u++) q[u] = sorted[min(p0 + u * 64 + lane, v.y - 1)];
+      for (uint32_t u = 0; u < 4; u++) q[u] = a.sorted[min(p0 + u * 64 + lane, v.y - 1)];
 #pragma unroll
       for (uint32_t u = 0; u < 4; u++) {
         const uint32_t w = q[u] >> 6;
@@ -608,8 +634,8 @@ __device__ __forceinline__ void ip_rows_range_blk(uint32_t Rr, uint32_t W, const
     const bool in = c * 64 + 63 >= lo_w && c * 64 < hi_w;  // wave-uniform: the chunk meets the window
     const uint64_t v = in && w >= lo_w && w < hi_w ? row[w - t.sw0] : 0ull;
     const uint64_t nz = __ballot(v != 0);
-    if (nz && w < W) PM[uint64_t(j) * W + w] = v;  // chunk-dense: every word of a chunk with a bit
-    if (lane == 0) cnz[uint64_t(j) * cw + c] = nz ? 1u : 0u;
+    if (nz && w < W) cm.PM[uint64_t(j) * W + w] = v;  // chunk-dense: every word of a chunk with a bit
+    if (lane == 0) cm.cnz[uint64_t(j) * cw + c] = nz ? 1u : 0u;
     if (nz) {
       lo = min(lo, c * 64 + uint32_t(__ffsll((unsigned long long)nz) - 1));
       hi = max(hi, c * 64 + 63 - uint32_t(__clzll((long long)nz)));
@@ -617,16 +643,12 @@ __device__ __forceinline__ void ip_rows_range_blk(uint32_t Rr, uint32_t W, const
     }
   }
   if (lane == 0) {  // the row's only writer: its span and nonzero-chunk mask (as k_ip_rows_fast's atomics leave them)
-    rng[4 * j] = lo;
-    rng[4 * j + 1] = lo == 0xFFFFFFFFu ? 0xFFFFFFFFu : ~hi;
-    reinterpret_cast<unsigned long long*>(rng)[2 * j + 1] = ~chunks;
+    cm.rng[4 * j] = lo;
+    cm.rng[4 * j + 1] = lo == 0xFFFFFFFFu ? 0xFFFFFFFFu : ~hi;
+    reinterpret_cast<unsigned long long*>(cm.rng)[2 * j + 1] = ~chunks;
   }
 }
-__global__ __launch_bounds__(256) void k_ip_rows_range(uint32_t Rr, uint32_t W, const DIPRange* __restrict__ rt, const uint2* __restrict__ iv,
-                                                       const uint32_t* __restrict__ sorted, uint64_t* __restrict__ PM,
-                                                       uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz, uint32_t c0, uint32_t nch) {
-  ip_rows_range_blk(Rr, W, rt, iv, sorted, PM, rng, cnz, blockIdx.x, c0, nch);
-}
+__global__ __launch_bounds__(256) void k_ip_rows_range(PeerCommon c, IpRangeArgs a) { ip_rows_range_blk(c, a, blockIdx.x); }
 
 // IP rows as pod intervals (no-panic runs whose network family is address-monotone in pod order, the
 // usual case: addresses handed out in pod order).  The host's address index turns the network less
@@ -647,14 +669,22 @@ __device__ __forceinline__ uint64_t pod_span_bits(uint32_t w, uint32_t x, uint32
   const uint32_t lo = a - b0, n = b - a;
   return (n == 64 ? ~0ull : ((1ull << n) - 1)) << lo;
 }
-__device__ __forceinline__ void ip_rows_iv_blk(uint32_t Rv, uint32_t W, const DIPIv* __restrict__ rt,
-                                               const uint2* __restrict__ iv, const DWordIP* __restrict__ words,
-                                               uint64_t* __restrict__ PM, uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz,
-                                               uint32_t bid_, uint32_t c0, uint32_t nch) {
+struct IpIvArgs {
+  uint32_t nb, Rv;
+  const DIPIv* rt;
+  const uint2* iv;
+  uint32_t c0, nch;
+};
+// (restrict does not reach struct members: the rows' own pointers come as restrict parameters, so the
+// wave-uniform loads that follow a row store in the loops stay scalar)
+__device__ __forceinline__ void ip_rows_iv_rows(const PeerCommon& cm, const IpIvArgs& a, uint64_t* __restrict__ PM,
+                                                uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz, uint32_t bid_) {
+  const uint32_t W = cm.W, c0 = a.c0, nch = a.nch;
+  const uint2* iv = a.iv;
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t r = __builtin_amdgcn_readfirstlane(bid_ * 4 + (threadIdx.x >> 6));  // wave-uniform
-  if (r >= Rv) return;
-  const DIPIv t = rt[r];
+  if (r >= a.Rv) return;
+  const DIPIv t = a.rt[r];
   const uint32_t j = t.peer, cw = (W + 63) / 64;
   // the rows' pod span [p0, p1) -> its chunks [s0, s1] (empty: s0 > s1)
   const uint32_t p0 = t.ivcnt ? iv[t.ivoff].x : 0u, p1 = t.ivcnt ? iv[t.ivoff + t.ivcnt - 1].y : 0u;
@@ -668,7 +698,7 @@ __device__ __forceinline__ void ip_rows_iv_blk(uint32_t Rv, uint32_t W, const DI
     const uint32_t w = c * 64 + lane;
     uint64_t v = 0;
     if (w < W) {
-      const DWordIP& wd = words[w];
+      const DWordIP& wd = cm.words[w];
       const uint64_t fm = t.fam ? wd.m6 : wd.m4;
       for (uint32_t i = 0; i < t.ivcnt; i++) {  // (scalar loads: the intervals are wave-uniform)
         const uint2 x = iv[t.ivoff + i];
@@ -691,11 +721,10 @@ __device__ __forceinline__ void ip_rows_iv_blk(uint32_t Rv, uint32_t W, const DI
     reinterpret_cast<unsigned long long*>(rng)[2 * j + 1] = ~chunks;
   }
 }
-__global__ __launch_bounds__(256) void k_ip_rows_iv(uint32_t Rv, uint32_t W, const DIPIv* __restrict__ rt, const uint2* __restrict__ iv,
-                                                    const DWordIP* __restrict__ words, uint64_t* __restrict__ PM,
-                                                    uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz, uint32_t c0, uint32_t nch) {
-  ip_rows_iv_blk(Rv, W, rt, iv, words, PM, rng, cnz, blockIdx.x, c0, nch);
+__device__ __forceinline__ void ip_rows_iv_blk(const PeerCommon& c, const IpIvArgs& a, uint32_t bid_) {
+  ip_rows_iv_rows(c, a, c.PM, c.rng, c.cnz, bid_);
 }
+__global__ __launch_bounds__(256) void k_ip_rows_iv(PeerCommon c, IpIvArgs a) { ip_rows_iv_blk(c, a, blockIdx.x); }
 
 // A block handles one group of `grp` IP peers over 4 chunks of 64 words (a wave per chunk, lane =
 // word): the group's tests and their except records are staged into LDS once (one coalesced load
@@ -703,11 +732,8 @@ __global__ __launch_bounds__(256) void k_ip_rows_iv(uint32_t Rv, uint32_t W, con
 // its words' [min, max] records once for the whole group.
 constexpr uint32_t IP_GROUP = 16;  // IP peers per block (profiles/r02_ip_group_ab.txt)
 // Chunks [c0, c0 + nch) of the rows (a source shard's ingress peers: the chunks of its word window).
-__device__ __forceinline__ void ip_rows_fast_blk(uint32_t Ri, uint32_t P, uint32_t W, const DIPTest* __restrict__ tests,
-                                                      const DCidr* __restrict__ ip_ex, const DIP* __restrict__ pod_ip,
-                                                      const DWordIP* __restrict__ words, uint64_t* __restrict__ PM,
-                                                      uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz, uint32_t bid_, uint32_t nblk_,
-                                                      uint32_t grp, uint32_t c0, uint32_t nch) {
+__device__ __forceinline__ void ip_rows_fast_blk(const PeerCommon& c, const IpArgs& a, uint32_t bid_) {
+  const uint32_t Ri = a.Ri, P = c.P, W = c.W, grp = a.grp, c0 = a.c0, nch = a.nch;
   DIPTest* const s_t = ip_lds.fast.t;
   DCidr* const s_ex = ip_lds.fast.ex;
   const uint32_t lane = threadIdx.x & 63;
@@ -719,15 +745,15 @@ __device__ __forceinline__ void ip_rows_fast_blk(uint32_t Ri, uint32_t P, uint32
   // staging below instead of following its barrier
   const uint32_t w = chunk * 64 + lane;
   const bool valid = w < W && chunk < c0 + nch;
-  const DWordIP wd = words[min(w, W - 1)];
+  const DWordIP wd = c.words[min(w, W - 1)];
   // the chunk's own [min, max] per family (records W.. of `words`): a peer whose network misses
   // the whole chunk leaves all 64 words zero — the wave only clears the chunk's cnz mask
-  const DWordIP ck = words[W + min(uint32_t(__builtin_amdgcn_readfirstlane(chunk)), (W + 63) / 64 - 1)];
-  const uint32_t ex0 = tests[r0].exoff, nex = tests[r0 + nr - 1].exoff + tests[r0 + nr - 1].excnt - ex0;
+  const DWordIP ck = c.words[W + min(uint32_t(__builtin_amdgcn_readfirstlane(chunk)), (W + 63) / 64 - 1)];
+  const uint32_t ex0 = a.tests[r0].exoff, nex = a.tests[r0 + nr - 1].exoff + a.tests[r0 + nr - 1].excnt - ex0;
   const bool ex_lds = nex <= IP_EX_LDS;
-  for (uint32_t x = threadIdx.x; x < nr; x += blockDim.x) s_t[x] = tests[r0 + x];
+  for (uint32_t x = threadIdx.x; x < nr; x += blockDim.x) s_t[x] = a.tests[r0 + x];
   if (ex_lds)
-    for (uint32_t x = threadIdx.x; x < nex; x += blockDim.x) s_ex[x] = ip_ex[ex0 + x];
+    for (uint32_t x = threadIdx.x; x < nex; x += blockDim.x) s_ex[x] = c.ip_ex[ex0 + x];
   __syncthreads();
   if (chunk >= c0 + nch) return;
   // the chunk test of the group's peers a lane each (lane x: peer r0 + x; grp <= 64): a peer whose
@@ -739,20 +765,14 @@ __device__ __forceinline__ void ip_rows_fast_blk(uint32_t Ri, uint32_t P, uint32
     const bool v4 = tx.cidr.fam == 4;
     touch = !(tx.cidr.valid && (v4 ? !ck.m4 || span_vs_cidr4(ck.min4, ck.max4, tx.cidr) == 0
                                    : !ck.m6 || span_vs_cidr6(ck.min6, ck.max6, tx.cidr) == 0));
-    if (!touch) cnz[uint64_t(tx.peer) * ((W + 63) / 64) + chunk] = 0;
+    if (!touch) c.cnz[uint64_t(tx.peer) * ((W + 63) / 64) + chunk] = 0;
   }
   for (uint64_t todo = __ballot(touch); todo; todo &= todo - 1) {
     const DIPTest t = s_t[__builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1)];
-    ip_row_word(t, ex_lds ? s_ex + (t.exoff - ex0) : ip_ex + t.exoff, pod_ip, wd, valid, w, chunk, P, W, lane, PM, rng, cnz);
+    ip_row_word(t, ex_lds ? s_ex + (t.exoff - ex0) : c.ip_ex + t.exoff, c.pod_ip, wd, valid, w, chunk, P, W, lane, c.PM, c.rng, c.cnz);
   }
 }
-__global__ __launch_bounds__(256) void k_ip_rows_fast(uint32_t Ri, uint32_t P, uint32_t W, const DIPTest* __restrict__ tests,
-                                                      const DCidr* __restrict__ ip_ex, const DIP* __restrict__ pod_ip,
-                                                      const DWordIP* __restrict__ words, uint64_t* __restrict__ PM,
-                                                      uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz, uint32_t grp,
-                                                      uint32_t c0, uint32_t nch) {
-  ip_rows_fast_blk(Ri, P, W, tests, ip_ex, pod_ip, words, PM, rng, cnz, blockIdx.x, gridDim.x, grp, c0, nch);
-}
+__global__ __launch_bounds__(256) void k_ip_rows_fast(PeerCommon c, IpArgs a) { ip_rows_fast_blk(c, a, blockIdx.x); }
 
 // IP rows as work items (the fused front's default, cyc_set_option "ip_items"): the host lists, per
 // 64-word chunk of the run's window, the IP rows whose network meets the chunk's address range
@@ -764,26 +784,22 @@ struct DIPItem {
   uint32_t chunk, off, cnt, touch;  // rows ilist[off .. off + cnt) (indices into the segment's tests)
 };
 constexpr uint32_t IPI_TOUCH = 16;  // touching rows per wave
-__device__ __forceinline__ void ip_rows_items_blk(uint32_t n_items, const DIPItem* __restrict__ items,
-                                                  const uint32_t* __restrict__ ilist, uint32_t P, uint32_t W,
-                                                  const DIPTest* __restrict__ tests, const DCidr* __restrict__ ip_ex,
-                                                  const DIP* __restrict__ pod_ip, const DWordIP* __restrict__ words,
-                                                  uint64_t* __restrict__ PM, uint32_t* __restrict__ rng, uint32_t* __restrict__ cnz,
-                                                  uint32_t bid_) {
+__device__ __forceinline__ void ip_rows_items_blk(const PeerCommon& c, const IpArgs& a, uint32_t bid_) {
+  const uint32_t P = c.P, W = c.W;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(bid_ * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  if (wv >= n_items) return;
-  const DIPItem it = items[wv];
+  if (wv >= a.n_items) return;
+  const DIPItem it = a.items[wv];
   const uint32_t cw = (W + 63) / 64;
-  const uint32_t mi = ilist[it.off + min(lane, it.cnt - 1)];
+  const uint32_t mi = a.ilist[it.off + min(lane, it.cnt - 1)];
   if (!it.touch) {
-    const uint32_t peer = tests[mi].peer;
-    if (lane < it.cnt) cnz[uint64_t(peer) * cw + it.chunk] = 0;
+    const uint32_t peer = a.tests[mi].peer;
+    if (lane < it.cnt) c.cnz[uint64_t(peer) * cw + it.chunk] = 0;
     return;
   }
   const uint32_t w = it.chunk * 64 + lane;
   const bool valid = w < W;
-  const DWordIP wd = words[min(w, W - 1)];
-  const DIPTest mine = tests[mi];  // lane x < cnt holds row x's test
+  const DWordIP wd = c.words[min(w, W - 1)];
+  const DIPTest mine = a.tests[mi];  // lane x < cnt holds row x's test
   for (uint32_t x = 0; x < it.cnt; x++) {
     DIPTest t;
     t.peer = __builtin_amdgcn_readlane(mine.peer, x);
@@ -798,13 +814,8 @@ __device__ __forceinline__ void ip_rows_items_blk(uint32_t n_items, const DIPIte
       t.cidr.net[i] = __builtin_amdgcn_readlane(mine.cidr.net[i], x);
       t.cidr.mask[i] = __builtin_amdgcn_readlane(mine.cidr.mask[i], x);
     }
-    ip_row_word(t, ip_ex + t.exoff, pod_ip, wd, valid, w, it.chunk, P, W, lane, PM, rng, cnz);
+    ip_row_word(t, c.ip_ex + t.exoff, c.pod_ip, wd, valid, w, it.chunk, P, W, lane, c.PM, c.rng, c.cnz);
   }
-}
-
-// Grid of k_ip_rows_fast / an IP-row range of k_front_b: peer groups x blocks of 4 of the nch chunks.
-__host__ __device__ inline uint64_t ip_rows_blocks(uint32_t Ri, uint32_t nch, uint32_t grp) {
-  return uint64_t((Ri + grp - 1) / grp) * ((nch + 3) / 4);
 }
 
 }  // namespace cyc

@@ -52,15 +52,21 @@ __device__ uint8_t eval_selector(const uint32_t* __restrict__ sel_off, const DRe
   return 1;
 }
 
-// sel_list (optional): only these selectors' rows are evaluated (range plan); S = its length.
-__global__ void k_selectors(uint32_t S, uint32_t L, const uint32_t* sel_off, const DReq* reqs, const uint32_t* req_vals,
-                            const uint32_t* ls_off, const uint32_t* ls_key, const uint32_t* ls_val,
-                            uint8_t* __restrict__ selres, const uint32_t* __restrict__ sel_list = nullptr) {
-  uint64_t n = uint64_t(S) * L;
+// One struct for both selector kernels: the dense one reads (dreqs in reqs, LVT), the label-set walk
+// (reqs, ls_off / ls_key / ls_val).  sel_list (optional): only these selectors' rows are evaluated
+// (range plan); S = its length.
+struct SelArgs {
+  uint32_t nb, S, L;
+  const uint32_t *sel_off, *req_vals, *LVT, *ls_off, *ls_key, *ls_val, *sel_list;
+  const DReq* reqs;
+  uint8_t* selres;
+};
+__global__ void k_selectors(SelArgs a) {
+  uint64_t n = uint64_t(a.S) * a.L;
   for (uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
-    uint32_t s = uint32_t(i / L), l = uint32_t(i % L);
-    if (sel_list) s = sel_list[s];
-    selres[uint64_t(s) * L + l] = eval_selector(sel_off, reqs, req_vals, ls_off, ls_key, ls_val, s, l);
+    uint32_t s = uint32_t(i / a.L), l = uint32_t(i % a.L);
+    if (a.sel_list) s = a.sel_list[s];
+    a.selres[uint64_t(s) * a.L + l] = eval_selector(a.sel_off, a.reqs, a.req_vals, a.ls_off, a.ls_key, a.ls_val, s, l);
   }
 }
 
@@ -69,22 +75,20 @@ __global__ void k_selectors(uint32_t S, uint32_t L, const uint32_t* sel_off, con
 // the key replaced by its dense index.  One coalesced load per requirement instead of a binary
 // search over the label set (a chain of dependent loads).
 constexpr uint32_t SEL_LPT = 4;  // label sets per thread in k_selectors_dense (independent loads in flight)
-__device__ __forceinline__ void selectors_dense_blk(uint32_t S, uint32_t L, const uint32_t* __restrict__ sel_off,
-                                                         const DReq* __restrict__ dreqs, const uint32_t* __restrict__ req_vals,
-                                                         const uint32_t* __restrict__ LVT, uint8_t* __restrict__ selres,
-                                                         const uint32_t* __restrict__ sel_list, uint32_t bid_, uint32_t nblk_) {
+__device__ __forceinline__ void selectors_dense_blk(const SelArgs& a, uint32_t bid_) {
+  const uint32_t L = a.L;
   // block = (selector, 256 * SEL_LPT label sets): the requirement walk is block-uniform (scalar
   // loads); each thread evaluates SEL_LPT label sets with their table loads issued together
   const uint32_t lchunks = (L + 256 * SEL_LPT - 1) / (256 * SEL_LPT);
   uint32_t s = bid_ / lchunks;
   const uint32_t l0 = (bid_ % lchunks) * 256 * SEL_LPT + threadIdx.x;
-  if (s >= S) return;
-  if (sel_list) s = sel_list[s];
+  if (s >= a.S) return;
+  if (a.sel_list) s = a.sel_list[s];
   uint8_t res[SEL_LPT];
 #pragma unroll
   for (uint32_t x = 0; x < SEL_LPT; x++) res[x] = 1;
-  for (uint32_t r = sel_off[s]; r < sel_off[s + 1]; r++) {
-    const DReq q = dreqs[r];
+  for (uint32_t r = a.sel_off[s]; r < a.sel_off[s + 1]; r++) {
+    const DReq q = a.reqs[r];
     if (q.op == REQ_INVALID) {  // reached only by label sets every earlier requirement matched
 #pragma unroll
       for (uint32_t x = 0; x < SEL_LPT; x++) res[x] = res[x] == 1 ? 2 : res[x];
@@ -94,9 +98,9 @@ __device__ __forceinline__ void selectors_dense_blk(uint32_t S, uint32_t L, cons
 #pragma unroll
     for (uint32_t x = 0; x < SEL_LPT; x++) {
       const uint32_t l = l0 + x * 256;
-      v[x] = l < L ? LVT[uint64_t(q.key) * L + l] : 0xFFFFFFFFu;
+      v[x] = l < L ? a.LVT[uint64_t(q.key) * L + l] : 0xFFFFFFFFu;
     }
-    const uint32_t v0 = (q.op == REQ_EQ || q.op == REQ_EQ_EMPTY) ? req_vals[q.voff] : 0u;
+    const uint32_t v0 = (q.op == REQ_EQ || q.op == REQ_EQ_EMPTY) ? a.req_vals[q.voff] : 0u;
 #pragma unroll
     for (uint32_t x = 0; x < SEL_LPT; x++) {
       const bool present = v[x] != 0xFFFFFFFFu;
@@ -107,7 +111,7 @@ __device__ __forceinline__ void selectors_dense_blk(uint32_t S, uint32_t L, cons
         case REQ_IN:
         case REQ_NOTIN: {
           bool in = false;
-          for (uint32_t j = 0; j < q.vcnt; j++) in |= (req_vals[q.voff + j] == v[x]);
+          for (uint32_t j = 0; j < q.vcnt; j++) in |= (a.req_vals[q.voff + j] == v[x]);
           ok = present && (q.op == REQ_IN ? in : !in);
           break;
         }
@@ -120,13 +124,10 @@ __device__ __forceinline__ void selectors_dense_blk(uint32_t S, uint32_t L, cons
 #pragma unroll
   for (uint32_t x = 0; x < SEL_LPT; x++) {
     const uint32_t l = l0 + x * 256;
-    if (l < L) selres[uint64_t(s) * L + l] = res[x];
+    if (l < L) a.selres[uint64_t(s) * L + l] = res[x];
   }
 }
-__global__ __launch_bounds__(256) void k_selectors_dense(uint32_t S, uint32_t L, const uint32_t* __restrict__ sel_off,
-                                                         const DReq* __restrict__ dreqs, const uint32_t* __restrict__ req_vals,
-                                                         const uint32_t* __restrict__ LVT, uint8_t* __restrict__ selres,
-                                                         const uint32_t* __restrict__ sel_list) { selectors_dense_blk(S, L, sel_off, dreqs, req_vals, LVT, selres, sel_list, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void k_selectors_dense(SelArgs a) { selectors_dense_blk(a, blockIdx.x); }
 
 // A selector's outcome on a label set, from SELRES (dense builds) or evaluated on the spot from the
 // dense label table (lazy builds: PM builds, whose pods carry ~as many label sets as there are pods,
@@ -220,11 +221,16 @@ __device__ __forceinline__ uint64_t hash_slots(uint64_t h, const uint8_t* __rest
 // of consecutive pods, instead of a pod -> label set -> table gather chain.
 __device__ __forceinline__ uint32_t sel_at_pod(const SelView& v, uint32_t s, uint32_t q) { return sel_eval(v, v.PLVT, v.P, s, q); }
 
-__device__ __forceinline__ void fill_u32_blk(uint32_t* p, uint64_t n, uint32_t v, uint32_t bid_, uint32_t nblk_) {
+struct FillArgs {
+  uint32_t nb, v;
+  uint32_t* p;
+  uint64_t n;
+};
+__device__ __forceinline__ void fill_u32_blk(const FillArgs& a, uint32_t bid_) {
   const uint64_t i = bid_ * uint64_t(blockDim.x) + threadIdx.x;
-  if (i < n) p[i] = v;
+  if (i < a.n) a.p[i] = a.v;
 }
-__global__ void k_fill_u32(uint32_t* p, uint64_t n, uint32_t v) { fill_u32_blk(p, n, v, blockIdx.x, gridDim.x); }
+__global__ void k_fill_u32(FillArgs a) { fill_u32_blk(a, blockIdx.x); }
 
 // PLVT[kx][q] = LVT[kx][label set of pod q] (SelView::PLVT), one word per thread (grid-stride)
 __global__ __launch_bounds__(256) void k_plvt(const uint32_t* __restrict__ LVT, const uint32_t* __restrict__ pod_ls, uint32_t L,

@@ -725,13 +725,14 @@ static int run_query(cyc_ctx* c, const std::vector<QueryTraffic>& ts, uint8_t* o
   pan.alloc(std::max<size_t>(ts.size() * 4, 16));
   pid.alloc(std::max<size_t>(ts.size() * 4, 16));
   hipStream_t st = nullptr;
-  if (uint64_t(q.S) * q.L)
-    k_selectors<<<grid1(uint64_t(q.S) * q.L, 256), 256, 0, st>>>(q.S, q.L, sel_off.as<uint32_t>(), reqs.as<DReq>(),
-                                                                  req_vals.as<uint32_t>(), ls_off.as<uint32_t>(),
-                                                                  ls_key.as<uint32_t>(), ls_val.as<uint32_t>(),
-                                                                  selres.as<uint8_t>());
-  if (M) k_portok<<<grid1(uint64_t(M) * D, 256), 256, 0, st>>>(M, D, pms.as<DPortM>(), pents.as<DPortEntry>(), descs.as<DDesc>(),
-                                                              portok.as<uint8_t>());
+  SelArgs sa{};  // (every selector: no sel_list, no dense table)
+  sa.S = q.S, sa.L = q.L, sa.nb = grid1(uint64_t(q.S) * q.L, 256);
+  sa.sel_off = sel_off.as<uint32_t>(), sa.reqs = reqs.as<DReq>(), sa.req_vals = req_vals.as<uint32_t>();
+  sa.ls_off = ls_off.as<uint32_t>(), sa.ls_key = ls_key.as<uint32_t>(), sa.ls_val = ls_val.as<uint32_t>();
+  sa.selres = selres.as<uint8_t>();
+  launch(k_selectors, sa, st);
+  const PortArgs pa{grid1(uint64_t(M) * D, 256), M, D, pms.as<DPortM>(), pents.as<DPortEntry>(), descs.as<DDesc>(), portok.as<uint8_t>()};
+  launch(k_portok, pa, st);
   QueryArgs qa{};
   qa.n = uint32_t(ts.size());
   qa.L = q.L;

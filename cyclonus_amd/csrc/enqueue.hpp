@@ -3,126 +3,283 @@
 // static): included once, by engine.hip, in stage order.
 #pragma once
 
+#ifndef CYC_PHASE_GRID
+#define CYC_PHASE_GRID 1  // row phases: each class-row launch's grid sized by its phase's identities (0: all)
+#endif
+#ifndef CYC_PB_REC
+#define CYC_PB_REC 1  // identity-set waves read their rows' matcher records (pb_rec); 0: the peers' chains
+#endif
+
+// Stage builders.  Each front stage's argument struct is defined next to its *_blk body; x_args fills
+// it, block count nb included — the one place the stage's grid is computed.  The two-branch DAG
+// launches each struct as a kernel of its own (enq_common, enq_peer_rows), build_front places the
+// same structs into the fused launches.
+constexpr uint32_t NB_OVER = 0xFFFFFFFFu;  // a range of >= 2^30 blocks: no launch takes it (FrontLaunches::fits)
+static uint32_t nb32(uint64_t n) { return n < (1ull << 30) ? uint32_t(n) : NB_OVER; }
+template <class A>
+static void launch(void (*k)(A), const A& a, hipStream_t st) {
+  if (a.nb) k<<<a.nb, 256, 0, st>>>(a);
+}
+template <class A>
+static void launch(void (*k)(PeerCommon, A), const PeerCommon& pc, const A& a, hipStream_t st) {
+  if (a.nb) k<<<a.nb, 256, 0, st>>>(pc, a);
+}
+
+// the word spans and chunk masks of the IP rows and (pod_spans) of PM builds' sparse pod rows (cnz needs
+// no reset; k_ip_rows with panics keeps no spans)
+static FillArgs fill_args(cyc_ctx* c, bool pod_spans) {
+  FillArgs a{};
+  a.p = c->prep.ip_rng.as<uint32_t>();
+  a.v = 0xFFFFFFFFu;
+  a.n = !c->pb.may_err && (c->range.Ri || c->range.Rr || pod_spans) ? c->pb.peers.size() * 4 : 0;
+  a.nb = nb32((a.n + 255) / 256);
+  return a;
+}
+// 1. selectors x label sets (lazy: evaluated where used, no table)
+static SelArgs sel_args(cyc_ctx* c, bool lazy) {
+  Prepared& prep = c->prep;
+  const bool dense = prep.dense_sel;
+  SelArgs a{};
+  a.S = c->range.n_sel;
+  a.L = c->pb.L;
+  a.sel_off = prep.sel_off.as<uint32_t>();
+  a.reqs = dense ? prep.dreqs.as<DReq>() : prep.reqs.as<DReq>();
+  a.req_vals = prep.req_vals.as<uint32_t>();
+  a.LVT = prep.lvt.as<uint32_t>();
+  a.ls_off = prep.ls_off.as<uint32_t>();
+  a.ls_key = prep.ls_key.as<uint32_t>();
+  a.ls_val = prep.ls_val.as<uint32_t>();
+  a.selres = prep.selres.as<uint8_t>();
+  a.sel_list = c->range.sel_list.as<uint32_t>();
+  const uint64_t n = uint64_t(a.S) * a.L;
+  if (n && !lazy) a.nb = dense ? nb32(uint64_t(a.S) * ((a.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))) : grid1(n, 256);
+  return a;
+}
+// 3. port matchers x job descriptors, and their descriptor bit rows (direct: from the matchers)
+static PortArgs port_args(cyc_ctx* c) {
+  Prepared& prep = c->prep;
+  PortArgs a{};
+  a.M = uint32_t(c->pb.pms.size());
+  a.D = uint32_t(std::max<size_t>(c->pb.descs.size(), 1));
+  a.pms = prep.pms.as<DPortM>();
+  a.pents = prep.pents.as<DPortEntry>();
+  a.descs = prep.descs.as<DDesc>();
+  a.portok = prep.portok.as<uint8_t>();
+  a.nb = a.M && c->pb.descs.size() ? nb32((uint64_t(a.M) * a.D + 255) / 256) : 0u;
+  return a;
+}
+static PortBitsArgs port_bits_args(cyc_ctx* c, const Route& route, bool direct) {
+  PortBitsArgs a{};
+  a.t = port_args(c);
+  a.direct = direct;
+  a.portbits = c->prep.portbits.as<uint32_t>();
+  a.nb = a.t.nb && route.port_bits ? nb32((uint64_t(a.t.M) + 255) / 256) : 0u;
+  return a;
+}
+// 4. per-slot destination words
+static SlotWordsArgs slot_words_args(cyc_ctx* c) {
+  Prepared& prep = c->prep;
+  SlotWordsArgs a{};
+  a.P = c->pb.P;
+  a.K = c->pb.K;
+  a.W = c->pb.W;
+  a.D = uint32_t(std::max<size_t>(c->pb.descs.size(), 1));
+  a.slot_desc = prep.slot_desc.as<int32_t>();
+  a.slot_status = prep.slot_status.as<uint8_t>();
+  a.VALID = prep.VALID.as<uint64_t>();
+  a.DESCW = prep.DESCW.as<int32_t>();
+  a.DM = prep.DM.as<uint64_t>();
+  a.nb = nb32((uint64_t(a.K) * a.W + 3) / 4);
+  return a;
+}
+
+// 2. peer rows: pod peers in identity space, expanded over word runs (skipped in IDO mode: the class
+// rows expand them); IP peers per pod.
+static PeerCommon peer_common(cyc_ctx* c) {
+  Prepared& prep = c->prep;
+  PeerCommon a{};
+  a.P = c->pb.P;
+  a.W = c->pb.W;
+  a.E = prep.dir[1].n;
+  a.EW = (a.E + 63) / 64;
+  a.PM = prep.PM.as<uint64_t>();
+  a.ER = prep.ER.as<uint64_t>();
+  a.rng = prep.ip_rng.as<uint32_t>();
+  a.cnz = ip_cnz(c);
+  a.peers = prep.peers.as<DPeer>();
+  a.sv = sel_view(c);
+  a.id_ns = prep.dir[1].id_ns.as<uint32_t>();
+  a.id_nsls = prep.id_nsls.as<uint32_t>();
+  a.id_ls = prep.dir[1].id_ls.as<uint32_t>();
+  a.pod_eid = prep.dir[1].pod_id.as<uint32_t>();
+  a.pod_ns = prep.pod_ns.as<uint32_t>();
+  a.pod_nsls = prep.pod_nsls.as<uint32_t>();
+  a.pod_ls = prep.pod_ls.as<uint32_t>();
+  a.nsw = prep.ns_words.as<DWordNS>();
+  a.words = prep.ip_words.as<DWordIP>();
+  a.pod_ip = prep.pod_ip.as<DIP>();
+  a.ip_ex = c->range.ip_ex.as<DCidr>();
+  a.req_post = prep.req_post.as<uint4>();
+  a.post_pods = prep.post_pods.as<uint32_t>();
+  return a;
+}
+// Segment x = 0, 1 of the IP rows and per-pod pod rows: direction x's sub-list [dlo, dhi) with its own
+// word window (source shards; a source shard's ingress peers: its sources' words), or — one_window,
+// target-row runs — both directions' adjacent sub-lists in segment 0 and nothing in segment 1.
+struct PeerSeg {
+  int x, dlo, dhi;
+  uint32_t w0, nw, c0, nch;  // words [w0, w0 + nw) = 64-word chunks [c0, c0 + nch)
+};
+static PeerSeg peer_seg(const cyc_ctx* c, bool one_window, int x) {
+  PeerSeg s{};
+  s.x = x;
+  s.dlo = one_window ? 0 : x;
+  s.dhi = one_window ? (x ? 0 : 2) : x + 1;
+  peer_window(c->range, c->pb.W, one_window ? 1 : x, s.w0, s.nw);
+  peer_chunks(c->range, c->pb.W, one_window ? 1 : x, s.c0, s.nch);
+  return s;
+}
+// items: the range plan's work items of the segment (the fused front), when it has them
+static IpArgs ip_args(cyc_ctx* c, const PeerSeg& s, bool items) {
+  RangePlan& rp = c->range;
+  IpArgs a{};
+  a.Ri = rp.ri_off[s.dhi] - rp.ri_off[s.dlo];
+  a.tests = rp.ip_tests.as<DIPTest>() + rp.ri_off[s.dlo];
+  a.grp = IP_GROUP;
+  a.c0 = s.c0, a.nch = s.nch, a.w0 = s.w0, a.nw = s.nw;
+  if (!a.Ri || !s.nch) return a;
+  if (c->pb.may_err) {  // k_ip_rows<true>
+    // batch size: as many peers per block as keep >= ~2048 blocks in flight, at most IPB_BATCH
+    const uint64_t wch = (s.nw + 3) / 4;
+    const uint64_t nb_want = (2048 + wch - 1) / wch;
+    a.batch = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(IPB_BATCH, (a.Ri + nb_want - 1) / nb_want)));
+    a.nb = nb32(wch * ((a.Ri + a.batch - 1) / a.batch));
+  } else if (items && rp.ip_items) {
+    a.items = rp.ipi_items.as<DIPItem>() + rp.ipi_off[s.x];
+    a.n_items = rp.ipi_off[s.x + 1] - rp.ipi_off[s.x];
+    a.ilist = rp.ipi_list.as<uint32_t>();
+    a.nb = nb32((uint64_t(a.n_items) + 3) / 4);
+  } else {
+    a.nb = nb32(uint64_t((a.Ri + a.grp - 1) / a.grp) * ((s.nch + 3) / 4));  // peer groups x blocks of 4 chunks
+  }
+  return a;
+}
+static IpRangeArgs ip_range_args(cyc_ctx* c, const PeerSeg& s) {
+  RangePlan& rp = c->range;
+  IpRangeArgs a{};
+  a.Rr = rp.rr_off[s.dhi] - rp.rr_off[s.dlo];
+  a.rt = rp.ipr_tests.as<DIPRange>() + rp.rr_off[s.dlo];
+  a.iv = rp.ipr_iv.as<uint2>();
+  a.sorted = c->prep.ipsort.as<uint32_t>();
+  a.c0 = s.c0, a.nch = s.nch;
+  a.nb = a.Rr && s.nch ? nb32((uint64_t(a.Rr) + 3) / 4) : 0u;
+  return a;
+}
+static IpIvArgs ip_iv_args(cyc_ctx* c, const PeerSeg& s) {
+  RangePlan& rp = c->range;
+  IpIvArgs a{};
+  a.Rv = rp.rv_off[s.dhi] - rp.rv_off[s.dlo];
+  a.rt = rp.ipv_tests.as<DIPIv>() + rp.rv_off[s.dlo];
+  a.iv = rp.ipv_iv.as<uint2>();
+  a.c0 = s.c0, a.nch = s.nch;
+  a.nb = a.Rv && s.nch ? nb32((uint64_t(a.Rv) + 3) / 4) : 0u;
+  return a;
+}
+// identity sets of direction x (IDO builds): its distinct matchers only, the ingress ones over the
+// window's identity words
+static IdentArgs ident_args(cyc_ctx* c, int x) {
+  RangePlan& rp = c->range;
+  const uint32_t E = c->prep.dir[1].n, EW = (E + 63) / 64, u0 = rp.rpu_off[x];
+  IdentArgs a{};
+  a.Ru = rp.rpu_off[x + 1] - u0;
+  a.pod_peers = rp.pod_peers_u.as<uint32_t>() + u0;
+  a.idob = c->prep.idob.as<uint64_t>() + uint64_t(u0) * EW;
+  a.ew0 = x == 0 ? rp.ido_ew0 : 0u;
+  a.new_ = x == 0 ? rp.ido_ew1 - rp.ido_ew0 : EW;
+  a.grp_ns = rp.ido_grp_ns.as<uint2>() + rp.ido_goff[x];
+  a.word_ns = rp.ido_word_ns.as<uint2>();
+  a.pbrec = rp.pb_rec.p && CYC_PB_REC ? rp.pb_rec.as<uint4>() + 3 * uint64_t(u0) : nullptr;
+  a.nb = a.Ru && E && a.new_ ? nb32((uint64_t((a.Ru + PB_GROUP - 1) / PB_GROUP) * a.new_ + 3) / 4) : 0u;
+  return a;
+}
+// full pod-peer rows, a wave per (PR_DIRECT_G pod peers, word)
+static PodDirectArgs pod_direct_args(cyc_ctx* c, const PeerSeg& s) {
+  RangePlan& rp = c->range;
+  PodDirectArgs a{};
+  a.Rp = rp.rp_off[s.dhi] - rp.rp_off[s.dlo];
+  a.pod_peers = rp.pod_peers.as<uint32_t>() + rp.rp_off[s.dlo];
+  a.w0 = s.w0, a.nw = s.nw;
+  a.nb = a.Rp && c->prep.dir[1].n && s.nw ? nb32((uint64_t((a.Rp + PR_DIRECT_G - 1) / PR_DIRECT_G) * s.nw + 3) / 4) : 0u;
+  return a;
+}
+// pod-peer rows through identity outcomes and word runs (k_peer_ident, then k_pod_rows)
+static PodRunsArgs pod_runs_args(cyc_ctx* c, const PeerSeg& s) {
+  Prepared& prep = c->prep;
+  RangePlan& rp = c->range;
+  const uint32_t E = prep.dir[1].n, r0 = rp.rp_off[s.dlo];
+  PodRunsArgs a{};
+  a.Rp = rp.rp_off[s.dhi] - r0;
+  a.pod_peers = rp.pod_peers.as<uint32_t>() + r0;
+  a.ido = prep.ido.as<uint8_t>() + uint64_t(r0) * E;
+  a.word_off = prep.word_off.as<uint32_t>();
+  a.run_e = prep.run_e.as<uint32_t>();
+  a.run_mask = prep.run_mask.as<uint64_t>();
+  a.w0 = s.w0, a.nw = s.nw;
+  if (a.Rp && E && s.nw) a.nb_ident = grid1(uint64_t(a.Rp) * E, 256), a.nb = nb32(uint64_t((s.nw + 255) / 256) * a.Rp);
+  return a;
+}
+// PM builds' sparse pod-peer rows and posting-built rows (launch C), grp peers per block
+static PodSparseArgs pod_sparse_args(cyc_ctx* c, const PeerSeg& s, uint32_t grp) {
+  RangePlan& rp = c->range;
+  const uint32_t E = c->prep.dir[1].n;
+  const uint64_t cb = (s.nch + 3) / 4;
+  PodSparseArgs a{};
+  a.Rp = rp.scan_off[s.dhi] - rp.scan_off[s.dlo];
+  a.grp = grp;
+  a.plist = rp.pp_scan.as<uint32_t>() + rp.scan_off[s.dlo];
+  a.plist_post = rp.pp_post.as<uint32_t>() + rp.post_off[s.dlo];
+  a.c0 = s.c0, a.nch = s.nch;
+  a.nb = a.Rp && E && cb ? nb32((uint64_t(a.Rp) + grp - 1) / grp * cb) : 0u;
+  a.nb_post = E && s.nch ? rp.post_off[s.dhi] - rp.post_off[s.dlo] : 0u;  // a block per posting-built peer
+  return a;
+}
+
 // Pipeline pieces.  Steps 1, 3, 4 are shared; steps 2 and 5-7 run per direction (ingress peers,
 // targets, class rows and plane are disjoint from egress ones), so the two directions can run
 // as two independent branches: one direction's front hides under the other's HBM-bound emit.
 enum { COMMON_SELECTORS = 1, COMMON_PORTS = 2, COMMON_FILL = 4, COMMON_ALL = 7 };
 
 static void enq_common(cyc_ctx* c, hipStream_t st, int parts = COMMON_ALL) {
-  Problem& pb = c->pb;
-  Prepared& prep = c->prep;
-  RangePlan& rp = c->range;
-  const uint32_t P = pb.P, K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
-  const uint32_t M = uint32_t(pb.pms.size());
-  if ((parts & COMMON_FILL) && !pb.may_err && (rp.Ri || rp.Rr))  // IP-peer word spans (k_ip_rows_fast)
-    k_fill_u32<<<grid1(pb.peers.size() * 4, 256), 256, 0, st>>>(prep.ip_rng.as<uint32_t>(), pb.peers.size() * 4, 0xFFFFFFFFu);
-  if (!(parts & COMMON_SELECTORS)) goto ports;
-  // 1. selectors x label sets
-  if (uint64_t(rp.n_sel) * pb.L && prep.dense_sel)
-    k_selectors_dense<<<unsigned(uint64_t(rp.n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))), 256, 0, st>>>(
-        rp.n_sel, pb.L, prep.sel_off.as<uint32_t>(), prep.dreqs.as<DReq>(), prep.req_vals.as<uint32_t>(), prep.lvt.as<uint32_t>(),
-        prep.selres.as<uint8_t>(), rp.sel_list.as<uint32_t>());
-  else if (uint64_t(rp.n_sel) * pb.L)
-    k_selectors<<<grid1(uint64_t(rp.n_sel) * pb.L, 256), 256, 0, st>>>(
-        rp.n_sel, pb.L, prep.sel_off.as<uint32_t>(), prep.reqs.as<DReq>(), prep.req_vals.as<uint32_t>(),
-        prep.ls_off.as<uint32_t>(), prep.ls_key.as<uint32_t>(), prep.ls_val.as<uint32_t>(), prep.selres.as<uint8_t>(),
-        rp.sel_list.as<uint32_t>());
-ports:
+  if (parts & COMMON_FILL) launch(k_fill_u32, fill_args(c, false), st);
+  if (parts & COMMON_SELECTORS) launch(c->prep.dense_sel ? k_selectors_dense : k_selectors, sel_args(c, false), st);
   if (!(parts & COMMON_PORTS)) return;
-  // 3. port matchers x job descriptors
-  if (M && pb.descs.size())
-    k_portok<<<grid1(uint64_t(M) * D, 256), 256, 0, st>>>(M, D, prep.pms.as<DPortM>(), prep.pents.as<DPortEntry>(),
-                                                          prep.descs.as<DDesc>(), prep.portok.as<uint8_t>());
-  if (M && pb.descs.size() && c->route.port_bits)
-    k_portbits<<<(M + 255) / 256, 256, 0, st>>>(M, D, prep.portok.as<uint8_t>(), prep.portbits.as<uint32_t>());
-  // 4. per-slot destination words
-  if (uint64_t(K) * W)
-    k_slot_words<<<unsigned((uint64_t(K) * W + 3) / 4), 256, 0, st>>>(
-        P, K, W, D, prep.slot_desc.as<int32_t>(), prep.slot_status.as<uint8_t>(), prep.VALID.as<uint64_t>(),
-        prep.DESCW.as<int32_t>(), prep.DM.as<uint64_t>());
+  launch(k_portok, port_args(c), st);
+  launch(k_portbits, port_bits_args(c, c->route, false), st);
+  launch(k_slot_words, slot_words_args(c), st);
 }
 
-// 2. peer rows of direction d's peers: pod peers in identity space, expanded over word runs
-// (skipped in IDO mode: the class rows expand them); IP peers per pod
+// d = 2: both directions — in one launch (their peer sub-lists are adjacent) when they share a window
 enum { PEERS_POD = 1, PEERS_IP = 2 };
 static void enq_peer_rows(cyc_ctx* c, int d, hipStream_t st, int which = PEERS_POD | PEERS_IP) {
-  Problem& pb = c->pb;
-  Prepared& prep = c->prep;
-  RangePlan& rp = c->range;
-  const uint32_t P = pb.P, W = pb.W;
-  const uint32_t E = prep.dir[1].n;
-  uint64_t *PM = prep.PM.as<uint64_t>(), *ER = prep.ER.as<uint64_t>();
-  const uint32_t *id_ns = prep.dir[1].id_ns.as<uint32_t>(), *id_ls = prep.dir[1].id_ls.as<uint32_t>();  // egress identities
-  // d = 2: both directions in one launch (their peer sub-lists are adjacent) when they share a window
-  if (d == 2 && !c->route.one_window) {
-    enq_peer_rows(c, 0, st, which);
-    enq_peer_rows(c, 1, st, which);
-    return;
-  }
-  const int dlo = d == 2 ? 0 : d, dhi = d == 2 ? 2 : d + 1;
-  uint32_t w0, nw, c0, nch;  // the rows' word window (a source shard's ingress peers: its sources' words)
-  peer_window(rp, W, d == 2 ? 1 : d, w0, nw);
-  peer_chunks(rp, W, d == 2 ? 1 : d, c0, nch);
-  const uint32_t r0 = rp.rp_off[dlo], Rp = (which & PEERS_POD) ? rp.rp_off[dhi] - r0 : 0u;
-  if (Rp && E && W && c->route.ido) {
-    const uint32_t EW = (E + 63) / 64;
-    for (int x = dlo; x < dhi; x++) {  // per direction: its identity word window
-      const uint32_t u0 = rp.rpu_off[x], Ru = rp.rpu_off[x + 1] - u0;  // distinct matchers only
-      const uint32_t ew0 = x == 0 ? rp.ido_ew0 : 0u, new_ = x == 0 ? rp.ido_ew1 - rp.ido_ew0 : EW;
-      if (Ru && new_)
-        k_peer_bits<<<unsigned((uint64_t((Ru + PB_GROUP - 1) / PB_GROUP) * new_ + 3) / 4), 256, 0, st>>>(
-            Ru, E, EW, rp.pod_peers_u.as<uint32_t>() + u0, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(), pb.L,
-            id_ns, prep.id_nsls.as<uint32_t>(), id_ls, prep.idob.as<uint64_t>() + uint64_t(u0) * EW, ew0, new_,
-            rp.ido_grp_ns.as<uint2>() + rp.ido_goff[x], rp.ido_word_ns.as<uint2>());
+  const Route& route = c->route;
+  const bool err = c->pb.may_err;
+  PeerCommon pc = peer_common(c);
+  pc.sv.selres = c->prep.selres.as<uint8_t>();  // this path always builds the table (enq_common); its kernels read it
+  for (int x = d == 2 ? 0 : d; x < (d == 2 ? 2 : d + 1); x++) {
+    const PeerSeg s = peer_seg(c, d == 2 && route.one_window, x);
+    if ((which & PEERS_POD) && route.ido) {
+      for (int dx = s.dlo; dx < s.dhi; dx++) launch(k_peer_bits, pc, ident_args(c, dx), st);
+    } else if ((which & PEERS_POD) && route.pod_direct) {
+      launch(err ? k_pod_rows_direct<true> : k_pod_rows_direct<false>, pc, pod_direct_args(c, s), st);
+    } else if (which & PEERS_POD) {
+      const PodRunsArgs a = pod_runs_args(c, s);
+      if (a.nb) k_peer_ident<<<a.nb_ident, 256, 0, st>>>(pc, a);
+      launch(err ? k_pod_rows<true> : k_pod_rows<false>, pc, a, st);
     }
-  } else if (Rp && E && nw && c->route.pod_direct) {
-    const uint32_t* plist = rp.pod_peers.as<uint32_t>() + r0;
-    const unsigned g = unsigned((pod_direct_waves(Rp, nw) + 3) / 4);
-    const uint32_t* eid = prep.dir[1].pod_id.as<uint32_t>();
-    if (pb.may_err)
-      k_pod_rows_direct<true><<<g, 256, 0, st>>>(Rp, P, W, plist, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(), pb.L, eid,
-                                                 id_ns, prep.id_nsls.as<uint32_t>(), id_ls, PM, ER, w0, nw);
-    else
-      k_pod_rows_direct<false><<<g, 256, 0, st>>>(Rp, P, W, plist, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(), pb.L, eid,
-                                                  id_ns, prep.id_nsls.as<uint32_t>(), id_ls, PM, ER, w0, nw);
-  } else if (Rp && E && nw) {
-    const uint32_t* plist = rp.pod_peers.as<uint32_t>() + r0;
-    uint8_t* ido = prep.ido.as<uint8_t>() + uint64_t(r0) * E;
-    k_peer_ident<<<grid1(uint64_t(Rp) * E, 256), 256, 0, st>>>(Rp, E, plist, prep.peers.as<DPeer>(), prep.selres.as<uint8_t>(),
-                                                               pb.L, id_ns, prep.id_nsls.as<uint32_t>(), id_ls, ido);
-    unsigned g = unsigned(uint64_t((nw + 255) / 256) * Rp);
-    if (pb.may_err)
-      k_pod_rows<true><<<g, 256, 0, st>>>(Rp, E, W, plist, ido, prep.word_off.as<uint32_t>(), prep.run_e.as<uint32_t>(),
-                                          prep.run_mask.as<uint64_t>(), PM, ER, w0, nw);
-    else
-      k_pod_rows<false><<<g, 256, 0, st>>>(Rp, E, W, plist, ido, prep.word_off.as<uint32_t>(), prep.run_e.as<uint32_t>(),
-                                           prep.run_mask.as<uint64_t>(), PM, ER, w0, nw);
-  }
-  const uint32_t v0 = rp.rv_off[dlo], Rv = (which & PEERS_IP) ? rp.rv_off[dhi] - v0 : 0u;
-  if (Rv && nw)
-    k_ip_rows_iv<<<(Rv + 3) / 4, 256, 0, st>>>(Rv, W, rp.ipv_tests.as<DIPIv>() + v0, rp.ipv_iv.as<uint2>(),
-                                             prep.ip_words.as<DWordIP>(), PM, prep.ip_rng.as<uint32_t>(), ip_cnz(c), c0, nch);
-  const uint32_t q0 = rp.rr_off[dlo], Rr = (which & PEERS_IP) ? rp.rr_off[dhi] - q0 : 0u;
-  if (Rr && nw)
-    k_ip_rows_range<<<(Rr + 3) / 4, 256, 0, st>>>(Rr, W, rp.ipr_tests.as<DIPRange>() + q0, rp.ipr_iv.as<uint2>(),
-                                                prep.ipsort.as<uint32_t>(), PM, prep.ip_rng.as<uint32_t>(), ip_cnz(c), c0, nch);
-  const uint32_t i0 = rp.ri_off[dlo], Ri = (which & PEERS_IP) ? rp.ri_off[dhi] - i0 : 0u;
-  if (Ri && nw) {
-    const DIPTest* tests = rp.ip_tests.as<DIPTest>() + i0;
-    if (pb.may_err) {
-      // batch size: as many peers per block as keep >= ~2048 blocks in flight, at most IPB_BATCH
-      const uint64_t wch = (nw + 3) / 4;
-      const uint64_t nb_want = (2048 + wch - 1) / wch;
-      const uint32_t bat = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(IPB_BATCH, (Ri + nb_want - 1) / nb_want)));
-      unsigned g = unsigned(wch * ((Ri + bat - 1) / bat));
-      k_ip_rows<true><<<g, 256, 0, st>>>(Ri, P, W, tests, rp.ip_ex.as<DCidr>(), prep.pod_ip.as<DIP>(), PM,
-                                         ER, bat, w0, nw);
-    } else {
-      const uint32_t grp = IP_GROUP;
-      k_ip_rows_fast<<<unsigned(ip_rows_blocks(Ri, nch, grp)), 256, 0, st>>>(
-          Ri, P, W, tests, rp.ip_ex.as<DCidr>(), prep.pod_ip.as<DIP>(), prep.ip_words.as<DWordIP>(), PM,
-          prep.ip_rng.as<uint32_t>(), ip_cnz(c), grp, c0, nch);
-    }
+    if (!(which & PEERS_IP)) continue;
+    launch(k_ip_rows_iv, pc, ip_iv_args(c, s), st);
+    launch(k_ip_rows_range, pc, ip_range_args(c, s), st);
+    launch(err ? k_ip_rows<true> : k_ip_rows_fast, pc, ip_args(c, s, false), st);
   }
 }
 
@@ -148,13 +305,6 @@ static void enq_member(cyc_ctx* c, int d, hipStream_t st, bool clear = true) {
   else k_member<<<grid1(c->range.n_act[d], 128), 128, 0, st>>>(ma);
   k_classify<<<grid1(c->range.n_act[d], 256), 256, 0, st>>>(ma, dd.class_of.as<uint32_t>());
 }
-
-#ifndef CYC_PHASE_GRID
-#define CYC_PHASE_GRID 1  // row phases: each class-row launch's grid sized by its phase's identities (0: all)
-#endif
-#ifndef CYC_PB_REC
-#define CYC_PB_REC 1  // identity-set waves read their rows' matcher records (pb_rec); 0: the peers' chains
-#endif
 
 // 6. class rows of direction d
 // IDO class rows: representatives per block (cyc_set_option "class_rpb"; 0 = auto: 4, or more in
@@ -460,13 +610,12 @@ struct FrontLaunches {
   FrontB fb;
   FrontC fc;
   FrontRows fd, fe;
-  uint64_t ga = 0, gb = 0, gc = 0;     // blocks of launches A, B, C
   uint32_t nd[3][2], ne[3][2];         // blocks of launches D and E per direction: [0] one pass, [1] / [2] a row phase's
   size_t lds = 0, lds_uni = 0;         // launch E's LDS bytes (egress with one descriptor per slot: lds_uni)
   uint32_t* span_fill = nullptr;       // the IP rows' word spans, set to ~0 by a memset before the launches
   size_t span_fill_bytes = 0;          // (0: the previous run's emit reset them, or launch A does)
   bool phases = false;
-  bool fits = true;                    // every launch's block count below 2^31 (else the DAG path runs)
+  bool fits = true;                    // every range below 2^30 blocks, every launch below 2^31 (else the DAG path runs)
 };
 
 // Host arithmetic only: changes no context state and enqueues nothing.
@@ -477,8 +626,7 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
   Problem& pb = c->pb;
   Prepared& prep = c->prep;
   RangePlan& rp = c->range;
-  const uint32_t P = pb.P, K = pb.K, W = pb.W, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
-  const uint32_t M = uint32_t(pb.pms.size()), E = prep.dir[1].n, EW = (E + 63) / 64;
+  const uint32_t K = pb.K, D = uint32_t(std::max<size_t>(pb.descs.size(), 1));
   FrontLaunches fl{};
   fl.phases = phases;
   bool& fits = fl.fits;
@@ -492,150 +640,49 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
   FrontRows &fd = fl.fd, &fe = fl.fe;
   const bool ido = route.ido;
   // A: IP word spans | port table | slot words | selectors
-  fa.fill_p = prep.ip_rng.as<uint32_t>();
-  // the word spans and chunk masks of the IP rows and of PM builds' sparse pod rows (cnz needs no reset)
-  fa.fill_n = (rp.Ri || rp.Rr || (!ido && rp.Rp)) ? pb.peers.size() * 4 : 0;
-  fa.nb[0] = blocks((fa.fill_n + 255) / 256);
-  fa.M = M;
-  fa.D = D;
-  fa.P = P;
-  fa.K = K;
-  fa.W = W;
-  fa.pms = prep.pms.as<DPortM>();
-  fa.pents = prep.pents.as<DPortEntry>();
-  fa.descs = prep.descs.as<DDesc>();
-  fa.portok = prep.portok.as<uint8_t>();
-  fa.nb[1] = (M && pb.descs.size()) ? blocks((uint64_t(M) * D + 255) / 256) : 0u;
-  fa.slot_desc = prep.slot_desc.as<int32_t>();
-  fa.slot_status = prep.slot_status.as<uint8_t>();
-  fa.VALID = prep.VALID.as<uint64_t>();
-  fa.DESCW = prep.DESCW.as<int32_t>();
-  fa.DM = prep.DM.as<uint64_t>();
-  fa.nb[2] = route.slot_words ? blocks((uint64_t(K) * W + 3) / 4) : 0u;
-  fa.S = rp.n_sel;
-  fa.L = pb.L;
-  fa.sel_off = prep.sel_off.as<uint32_t>();
-  fa.dreqs = prep.dreqs.as<DReq>();
-  fa.req_vals = prep.req_vals.as<uint32_t>();
-  fa.LVT = prep.lvt.as<uint32_t>();
-  fa.selres = prep.selres.as<uint8_t>();
-  fa.sel_list = rp.sel_list.as<uint32_t>();
-  fa.nb[3] = uint64_t(rp.n_sel) * pb.L && !route.lazy_sel ? blocks(uint64_t(rp.n_sel) * ((pb.L + 256 * SEL_LPT - 1) / (256 * SEL_LPT))) : 0u;
+  const FillArgs fill = fill_args(c, !ido && rp.Rp);
+  const PortArgs ports = port_args(c);
+  SlotWordsArgs slots = slot_words_args(c);
+  if (!route.slot_words) slots.nb = 0;
+  fa.sel = sel_args(c, route.lazy_sel);
   // B: IP rows | pod-peer identity sets (both directions' adjacent sub-lists) | membership x 2
-  // Segments x = 0, 1 of the IP rows and per-pod pod rows: the directions' sub-lists with their own
-  // word windows (source shards), or both directions in segment 0 (one window)
-  const bool one_win = route.one_window;
-  fb.P = P;
-  fb.W = W;
-  fb.ip_ex = rp.ip_ex.as<DCidr>();
-  fb.pod_ip = prep.pod_ip.as<DIP>();
-  fb.words = prep.ip_words.as<DWordIP>();
-  fb.PM = prep.PM.as<uint64_t>();
-  fb.rng = prep.ip_rng.as<uint32_t>();
-  fb.cnz = ip_cnz(c);
-  fb.ip_grp = IP_GROUP;
-  fb.ipr_iv = rp.ipr_iv.as<uint2>();
-  fb.ipsort = prep.ipsort.as<uint32_t>();
-  fb.ipv_iv = rp.ipv_iv.as<uint2>();
-  fb.ip_ilist = rp.ipi_list.as<uint32_t>();
-  for (int x = 0; x < 2; x++) {
-    const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
-    const uint32_t i0 = rp.ri_off[dlo];
-    fb.Ri[x] = one_win && x ? 0u : rp.ri_off[dhi] - i0;
-    fb.tests[x] = rp.ip_tests.as<DIPTest>() + i0;
-    peer_chunks(c->range, c->pb.W, one_win ? 1 : x, fb.ic0[x], fb.inch[x]);
-    fb.nb[x] = fb.Ri[x] && fb.inch[x] ? blocks(ip_rows_blocks(fb.Ri[x], fb.inch[x], fb.ip_grp)) : 0u;
-    if (rp.ip_items && fb.nb[x]) {  // the range plan's work items of this segment
-      fb.ip_items[x] = rp.ipi_items.as<DIPItem>() + rp.ipi_off[x];
-      fb.n_ip_items[x] = rp.ipi_off[x + 1] - rp.ipi_off[x];
-      fb.nb[x] = blocks((uint64_t(fb.n_ip_items[x]) + 3) / 4);
-    }
-    fb.Rr[x] = one_win && x ? 0u : rp.rr_off[dhi] - rp.rr_off[dlo];
-    fb.rtests[x] = rp.ipr_tests.as<DIPRange>() + rp.rr_off[dlo];
-    fb.nb[9 + x] = fb.Rr[x] && fb.inch[x] ? blocks((uint64_t(fb.Rr[x]) + 3) / 4) : 0u;
-    fb.Rv[x] = one_win && x ? 0u : rp.rv_off[dhi] - rp.rv_off[dlo];
-    fb.vtests[x] = rp.ipv_tests.as<DIPIv>() + rp.rv_off[dlo];
-    fb.nb[11 + x] = fb.Rv[x] && fb.inch[x] ? blocks((uint64_t(fb.Rv[x]) + 3) / 4) : 0u;
-  }
-  fb.E = E;
-  fb.EW = EW;
-  fb.L = pb.L;
-  fb.peers = prep.peers.as<DPeer>();
-  fb.selres = prep.selres.as<uint8_t>();
-  fb.id_ns = prep.dir[1].id_ns.as<uint32_t>();
-  fb.id_nsls = prep.id_nsls.as<uint32_t>();
-  fb.id_ls = prep.dir[1].id_ls.as<uint32_t>();
-  fb.sv = sel_view(c);
-  fb.word_ns = rp.ido_word_ns.as<uint2>();
-  for (int x = 0; x < 2; x++) {  // identity sets per direction: the ingress ones over the window's identity words
-    const uint32_t ux = rp.rpu_off[x];
-    fb.Ru_[x] = rp.rpu_off[x + 1] - ux;
-    fb.pod_peers_u_[x] = rp.pod_peers_u.as<uint32_t>() + ux;
-    fb.idob_[x] = prep.idob.as<uint64_t>() + uint64_t(ux) * EW;
-    fb.grp_ns_[x] = rp.ido_grp_ns.as<uint2>() + rp.ido_goff[x];
-    fb.pbrec_[x] = rp.pb_rec.p && CYC_PB_REC ? rp.pb_rec.as<uint4>() + 3 * uint64_t(ux) : nullptr;
-    fb.ew0[x] = x == 0 ? rp.ido_ew0 : 0u;
-    fb.new_[x] = x == 0 ? rp.ido_ew1 - rp.ido_ew0 : EW;
-    fb.nb[2 + x] = (fb.Ru_[x] && E && fb.new_[x]) ? blocks((uint64_t((fb.Ru_[x] + PB_GROUP - 1) / PB_GROUP) * fb.new_[x] + 3) / 4) : 0u;
-  }
-  if (!ido && !route.pod_sparse) {  // PM builds, few pod-peer words: full rows, a wave per (pod peer, word)
-    fb.pod_direct = 1;
-    fb.pod_eid = prep.dir[1].pod_id.as<uint32_t>();
-    for (int x = 0; x < 2; x++) {
-      const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
-      fb.Rp[x] = one_win && x ? 0u : rp.rp_off[dhi] - rp.rp_off[dlo];
-      fb.plist[x] = rp.pod_peers.as<uint32_t>() + rp.rp_off[dlo];
-      peer_window(c->range, c->pb.W, one_win ? 1 : x, fb.pw0[x], fb.pnw[x]);
-      fb.nb[2 + x] = (fb.Rp[x] && E && fb.pnw[x]) ? blocks((pod_direct_waves(fb.Rp[x], fb.pnw[x]) + 3) / 4) : 0u;
-    }
-  } else if (!ido) {  // PM builds: sparse pod-peer rows in launch C (k_front_c)
-    fb.nb[2] = fb.nb[3] = 0;
-    fc.P = P;
-    fc.W = W;
-    fc.req_post = prep.req_post.as<uint4>();
-    fc.post_pods = prep.post_pods.as<uint32_t>();
-    fc.peers = prep.peers.as<DPeer>();
-    fc.pod_ns = prep.pod_ns.as<uint32_t>();
-    fc.pod_nsls = prep.pod_nsls.as<uint32_t>();
-    fc.pod_ls = prep.pod_ls.as<uint32_t>();
-    fc.nsw = prep.ns_words.as<DWordNS>();
-    fc.sv = sel_view(c);
-    fc.PM = prep.PM.as<uint64_t>();
-    fc.rng = prep.ip_rng.as<uint32_t>();
-    fc.cnz = ip_cnz(c);
+  fb.pc = peer_common(c);
+  uint32_t pr_grp = 0;
+  if (!ido && route.pod_sparse) {
     // a wave per chunk over groups of 8 peers once that fills the chip (>= 64k peer chunks:
     // config #3u 2.6 vs 3.2 ms), else the 4 waves of a block share each chunk (config #2)
     uint64_t peer_chunks_all = 0;
     for (int x = 0; x < 2; x++) {
-      const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
-      fc.Rp[x] = one_win && x ? 0u : rp.scan_off[dhi] - rp.scan_off[dlo];
-      fc.plist[x] = rp.pp_scan.as<uint32_t>() + rp.scan_off[dlo];
-      fc.plist_post[x] = rp.pp_post.as<uint32_t>() + rp.post_off[dlo];
-      peer_chunks(c->range, c->pb.W, one_win ? 1 : x, fc.c0[x], fc.nch[x]);
-      peer_chunks_all += uint64_t(fc.Rp[x]) * fc.nch[x];
+      const PeerSeg s = peer_seg(c, route.one_window, x);
+      peer_chunks_all += uint64_t(rp.scan_off[s.dhi] - rp.scan_off[s.dlo]) * s.nch;
     }
-    fc.pr_grp = c->opt.pr_group > 0 ? uint32_t(c->opt.pr_group) : (peer_chunks_all >= 65536 ? 8u : 1u);
-    for (int x = 0; x < 2; x++) {
-      const int dlo = one_win ? 0 : x, dhi = one_win ? 2 : x + 1;
-      const uint64_t cb = (fc.nch[x] + 3) / 4;
-      fc.nb[2 + x] = (fc.Rp[x] && E && cb) ? blocks((uint64_t(fc.Rp[x]) + fc.pr_grp - 1) / fc.pr_grp * cb) : 0u;
-      fc.nb[4 + x] = E && fc.nch[x] && !(one_win && x) ? rp.post_off[dhi] - rp.post_off[dlo] : 0u;  // a block per posting-built peer
-    }
+    pr_grp = c->opt.pr_group > 0 ? uint32_t(c->opt.pr_group) : (peer_chunks_all >= 65536 ? 8u : 1u);
+    fc.pc = fb.pc;
+  }
+  for (int x = 0; x < 2; x++) {
+    const PeerSeg s = peer_seg(c, route.one_window, x);
+    fb.ip[x] = ip_args(c, s, true);
+    fb.ip_range[x] = ip_range_args(c, s);
+    fb.ip_iv[x] = ip_iv_args(c, s);
+    if (ido) fb.ident[x] = ident_args(c, x);
+    // PM builds, few pod-peer words: full rows, a wave per (pod peer, word); else sparse pod-peer rows
+    // in launch C (k_front_c)
+    else if (!route.pod_sparse) fb.pods[x] = pod_direct_args(c, s);
+    else fc.pods[x] = pod_sparse_args(c, s, pr_grp);
   }
   size_t &lds = fl.lds, &lds_uni = fl.lds_uni, e_per[2] = {0, 0};
   uint32_t na_all[2];  // active identities per direction
   for (int d = 0; d < 2; d++) {
     const uint32_t na = na_all[d] = prep.dir[d].n ? rp.n_act[d] : 0u;
-    fb.ma[d] = member_args(c, d);
-    fc.ma[d] = fb.ma[d];
+    fb.member[d].a = fc.elect[d].a = member_args(c, d);
     if (phases) {  // the class election lists phase 2's classes apart (from the tail of reps[])
-      fc.ma[d].first_row = rp.arow[d].as<uint32_t>();
-      fc.ma[d].split = route.phase_split;
+      fc.elect[d].a.first_row = rp.arow[d].as<uint32_t>();
+      fc.elect[d].a.split = route.phase_split;
     }
-    fc.class_of[d] = prep.dir[d].class_of.as<uint32_t>();
-    fb.member_wave[d] = route.member_wave[d];
-    fb.nb[4 + d] = na ? blocks(fb.member_wave[d] ? (uint64_t(na) + 3) / 4 : (uint64_t(na) + 255) / 256) : 0u;
-    fc.nb[d] = na ? blocks((uint64_t(na) + 255) / 256) : 0u;
+    fc.elect[d].class_of = prep.dir[d].class_of.as<uint32_t>();
+    fb.member[d].wave = route.member_wave[d];
+    fb.member[d].nb = nb32(fb.member[d].wave ? (uint64_t(na) + 3) / 4 : (uint64_t(na) + 255) / 256);
+    fc.elect[d].nb = nb32((uint64_t(na) + 255) / 256);
     if (!na) continue;
     fd.ra[d] = row_args(c, d);  // its blocks empty the direction's hash table for the next run
     if (out_in && out_eg) {
@@ -646,14 +693,14 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
     // the election chain on every block — IDO identity sets C + D 29 -> 45 us, PM class rows C + D
     // 79 -> 117 us on config #4: profiles/r04_elect_ab.txt)
     if (!ido) {  // PM builds: launch D (k_front_d_pm) is the class rows from flattened peer lists
-      fd.nb[d] = pl_blocks(c, d);
+      fd.nb(d) = pl_blocks(c, d);
       if (d == 1 && prep.uni_desc && c->pb.blocks.empty()) fd.ra[d].udesc = prep.udesc.as<int32_t>();
       fd.ra[d].pod_sparse = route.pod_sparse;  // pod rows from pod_rows_sparse_blk (launch C)
       continue;
     }
     fe.ra[d] = fd.ra[d];
     fe.ra[d].ht_clear_words = 0;  // (launch D's identity sets empty it)
-    fd.nb[d] = blocks((uint64_t(na) * ((fd.ra[d].NB + CI_G - 1) / CI_G) + 3) / 4);
+    fd.nb(d) = blocks((uint64_t(na) * ((fd.ra[d].NB + CI_G - 1) / CI_G) + 3) / 4);
     // egress with one descriptor per slot (udesc): only the block's slots' sets are staged
     if (d == 1 && prep.uni_desc) fe.ra[d].udesc = prep.udesc.as<int32_t>();
     e_per[d] = ido_rep_lds(d == 0 || fe.ra[d].udesc ? uint32_t(E_KC) : D, fd.ra[d].EW);
@@ -682,48 +729,39 @@ static FrontLaunches build_front(cyc_ctx* c, const Route& route, uint64_t* out_i
   for (int d = 0; d < 2; d++) {
     if (!e_per[d]) continue;
     fe.ra[d].rpb = class_rpb(c, e_per[d], e_want);
-    fe.nb[d] = blocks(e_blocks(d, fe.ra[d].rpb));
+    fe.nb(d) = blocks(e_blocks(d, fe.ra[d].rpb));
     if (d == 1 && fe.ra[d].udesc) lds_uni = e_per[d] * fe.ra[d].rpb;
     else lds = std::max<size_t>(lds, e_per[d] * fe.ra[d].rpb);
   }
   // membership ahead of the rest of launch B unless the IP rows alone fill the chip (~2k resident blocks)
-  fb.member_first = uint64_t(fb.nb[0]) + fb.nb[1] < 2048;
-  const bool bits = fa.nb[1] && route.port_bits;
-  const uint32_t nb_bits = bits ? blocks((uint64_t(M) + 255) / 256) : 0u;
-  fb.M = M;
-  fb.D = D;
-  fb.portok = prep.portok.as<uint8_t>();
-  fb.portbits = prep.portbits.as<uint32_t>();
-  fb.nb[6] = nb_bits;
-  fe.ra[1].portbits = bits && fe.nb[1] ? prep.portbits.as<uint32_t>() : nullptr;
+  fb.member_first = uint64_t(fb.ip[0].nb) + fb.ip[1].nb < 2048;
   // Without a selector table to build (lazy selectors) launch A is dropped: its port table, slot
   // words and port bits (from the matchers directly) join launch B — their readers are the class
   // rows, launches D / E — and the IP rows' word spans were reset by the previous run's emit
   // (EmitArgs::reset; a memset when they were not).  Captured graphs keep launch A: a replay must not
   // depend on the step before it.
-  if (fa.nb[3] == 0 && !c->run.capturing) {
-    fb.pre = fa;
-    fb.bits_direct = 1;
-    fb.nb[7] = fa.nb[1];
-    fb.nb[8] = fa.nb[2];
-    if (fa.fill_n && !prep.ip_rng_clean) fl.span_fill = fa.fill_p, fl.span_fill_bytes = fa.fill_n * 4;
-    fa.nb[0] = fa.nb[1] = fa.nb[2] = 0;
+  const bool drop_a = fa.sel.nb == 0 && !c->run.capturing;
+  fb.port_bits = port_bits_args(c, route, drop_a);
+  fe.ra[1].portbits = fb.port_bits.nb && fe.nb_eg ? prep.portbits.as<uint32_t>() : nullptr;
+  if (drop_a) {
+    fb.port_table = ports, fb.slot_words = slots;
+    if (fill.n && !prep.ip_rng_clean) fl.span_fill = fill.p, fl.span_fill_bytes = fill.n * 4;
+  } else {
+    fa.fill = fill, fa.port_table = ports, fa.slot_words = slots;
   }
-  fl.ga = uint64_t(fa.nb[0]) + fa.nb[1] + fa.nb[2] + fa.nb[3];
-  for (uint32_t x : fb.nb) fl.gb += x;
-  for (uint32_t x : fc.nb) fl.gc += x;
   // the class rows' grids: one pass, or per row phase only the identities that can represent the
   // phase's classes (the representatives' first rows decide the phase), not every active identity
   for (uint32_t phase = 0; phase < 3; phase++)
     for (int d = 0; d < 2; d++) {
-      fl.nd[phase][d] = fd.nb[d];
-      fl.ne[phase][d] = fe.nb[d];
+      fl.nd[phase][d] = fd.nb(d);
+      fl.ne[phase][d] = fe.nb(d);
       if (!CYC_PHASE_GRID || !phase) continue;
       const uint32_t nph = phase == 1 ? rp.n_act_ph1[d] : na_all[d] - rp.n_act_ph1[d];
-      if (ido && fe.nb[d]) fl.ne[phase][d] = blocks(ido_row_blocks(fe.ra[d].WA, K, E_KC, nph, fe.ra[d].rpb));
-      else if (!ido && fd.nb[d]) fl.nd[phase][d] = std::min(fd.nb[d], nph);
+      if (ido && fe.nb(d)) fl.ne[phase][d] = blocks(ido_row_blocks(fe.ra[d].WA, K, E_KC, nph, fe.ra[d].rpb));
+      else if (!ido && fd.nb(d)) fl.nd[phase][d] = std::min(fd.nb(d), nph);
     }
-  fits = fits && fl.gb < (1ull << 31) && fl.gc < (1ull << 31);
+  // (a range of >= 2^30 blocks counts NB_OVER: its launch then fails the sum)
+  fits = fits && fa.blocks() < (1ull << 31) && fb.blocks() < (1ull << 31) && fc.blocks() < (1ull << 31);
   return fl;
 }
 
@@ -739,30 +777,30 @@ static void launch_front(cyc_ctx* c, hipStream_t st, FrontLaunches& fl, const Fr
   FrontRows &fd = fl.fd, &fe = fl.fe;
   const bool ido = c->route.ido;
   if (fl.span_fill) HIPCHK(hipMemsetAsync(fl.span_fill, 0xFF, fl.span_fill_bytes, st));
-  if (fl.ga) k_front_a<<<unsigned(fl.ga), 256, 0, st>>>(fl.fa);
-  if (fl.gb) k_front_b<<<unsigned(fl.gb), 256, 0, st>>>(fl.fb);
-  if (fl.gc) k_front_c<<<unsigned(fl.gc), 256, 0, st>>>(fl.fc);
+  if (fl.fa.blocks()) k_front_a<<<unsigned(fl.fa.blocks()), 256, 0, st>>>(fl.fa);
+  if (fl.fb.blocks()) k_front_b<<<unsigned(fl.fb.blocks()), 256, 0, st>>>(fl.fb);
+  if (fl.fc.blocks()) k_front_c<<<unsigned(fl.fc.blocks()), 256, 0, st>>>(fl.fc);
   if (ev.front) HIPCHK(hipEventRecord(ev.front, st));  // eager runs: phase timings
-  if (ido && fd.nb[0] + fd.nb[1]) k_front_d<<<fd.nb[0] + fd.nb[1], 256, 0, st>>>(fd);  // identity sets: once
+  if (ido && fd.nb_in + fd.nb_eg) k_front_d<<<fd.nb_in + fd.nb_eg, 256, 0, st>>>(fd);  // identity sets: once
   // the class rows: once, or per row phase with phase 1's emit between (mid)
   auto class_rows = [&](uint32_t phase) {
     for (int d = 0; d < 2; d++) {
       (ido ? fe : fd).ra[d].phase = phase;
-      fd.nb[d] = fl.nd[phase][d];
-      fe.nb[d] = fl.ne[phase][d];
+      fd.nb(d) = fl.nd[phase][d];
+      fe.nb(d) = fl.ne[phase][d];
     }
     const size_t lds = fl.lds, lds_uni = fl.lds_uni;
     if (!ido) {
-      const unsigned gd = fd.nb[0] + fd.nb[1];
+      const unsigned gd = fd.nb_in + fd.nb_eg;
       if (gd && c->route.pl_wave) k_front_d_pm<true><<<gd, pl_threads(c), 0, st>>>(fd);
       else if (gd) k_front_d_pm<false><<<gd, pl_threads(c), 0, st>>>(fd);
-    } else if (fe.nb[0] && fe.nb[1] && fe.ra[1].udesc) {
-      k_front_e_uni<<<fe.nb[0] + fe.nb[1], 256, std::max(lds, lds_uni), st>>>(fe);
+    } else if (fe.nb_in && fe.nb_eg && fe.ra[1].udesc) {
+      k_front_e_uni<<<fe.nb_in + fe.nb_eg, 256, std::max(lds, lds_uni), st>>>(fe);
     } else {  // the directions' class rows as two launches, each at its own register budget (egress 101
               // VGPRs, ingress 61: one launch at 101 ran config #3 189 -> 170 us, profiles/r03_e_split_ab.txt)
-      if (fe.nb[1] && fe.ra[1].udesc) k_class_rows_ido<true, E_KC, true><<<fe.nb[1], 256, lds_uni, st>>>(fe.ra[1]);
-      else if (fe.nb[1]) k_class_rows_ido<true, E_KC><<<fe.nb[1], 256, lds, st>>>(fe.ra[1]);
-      if (fe.nb[0]) k_class_rows_ido<false, E_KC><<<fe.nb[0], 256, lds, st>>>(fe.ra[0]);
+      if (fe.nb_eg && fe.ra[1].udesc) k_class_rows_ido<true, E_KC, true><<<fe.nb_eg, 256, lds_uni, st>>>(fe.ra[1]);
+      else if (fe.nb_eg) k_class_rows_ido<true, E_KC><<<fe.nb_eg, 256, lds, st>>>(fe.ra[1]);
+      if (fe.nb_in) k_class_rows_ido<false, E_KC><<<fe.nb_in, 256, lds, st>>>(fe.ra[0]);
     }
   };
   class_rows(fl.phases ? 1u : 0u);

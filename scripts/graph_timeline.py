@@ -15,7 +15,8 @@ if sys.argv[1] == "show":
     import sqlite3
 
     db = sqlite3.connect(sys.argv[2])
-    rows = db.execute("select s.kernel_name, d.start, d.end from rocpd_kernel_dispatch d join rocpd_info_kernel_symbol s "
+    rows = db.execute("select s.kernel_name, d.start, d.end, d.grid_size_x, d.workgroup_size_x "
+                      "from rocpd_kernel_dispatch d join rocpd_info_kernel_symbol s "
                       "on d.kernel_id = s.id order by d.start").fetchall()
     # replays end with the emit (and the graph's trailing copy, if any): the last replay = the kernels
     # after the second-to-last emit ended
@@ -33,9 +34,9 @@ if sys.argv[1] == "show":
               f"previous emit end -> first kernel {statistics.median(s[0] - s[2] for s in spans) / 1e3:.1f} us median")
     rows = rows[ends[-2] + 1:] if len(ends) > 1 else rows
     t0 = min(r[1] for r in rows)
-    for name, a, b in sorted(rows, key=lambda r: r[1]):
+    for name, a, b, grid, wg in sorted(rows, key=lambda r: r[1]):
         short = name.split("(")[0].replace("_ZN3cyc", "")[:48]
-        print(f"{(a - t0) / 1e3:9.1f} us -> {(b - t0) / 1e3:9.1f} us  ({(b - a) / 1e3:8.1f})  {short}")
+        print(f"{(a - t0) / 1e3:9.1f} us -> {(b - t0) / 1e3:9.1f} us  ({(b - a) / 1e3:8.1f})  {short}  grid {grid} / {wg}")
     sys.exit(0)
 
 import torch
