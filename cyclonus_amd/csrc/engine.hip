@@ -679,6 +679,7 @@ int cyc_get_option(cyc_ctx* c, const char* name, int64_t* value) {
     *value = c->route.emit_interleave ? 1 : 0;
   } else if (n == "plvt_active") *value = c->prep.plvt_ready ? 1 : 0;
   else if (n == "ip_iv_rows") *value = c->range.Rv;  // (the last range plan's interval-built rows)
+  else if (n == "ip_range_rows") *value = c->range.Rr;  // (... and its range-built rows)
   else if (n == "row_phases_active") *value = c->run.last.phase_used;  // (the last run's phases; 0: a plain run)
   else return fail(c, CYC_ERR_ARG, "unknown option " + n);
   return (int)CYC_OK;

@@ -436,8 +436,8 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  * cyc_get_option also reports "launch" (the graphs mode in effect), "row_phases_active" (the last
  * run's phases: 2, or 0), "front_fused_active", "pl_wave_active" (needs cyc_probe_prepare),
  * "class_inplace_active" and "emit_interleave_active" (the routes in effect; they need a run),
- * "plvt_active" and "ip_iv_rows" (the current range plan's
- * interval-built IP rows); "pod_words" reports the mode the prepared probe uses (0 or 1; needs
+ * "plvt_active", "ip_iv_rows" and "ip_range_rows" (the current range plan's
+ * interval-built and range-built IP rows); "pod_words" reports the mode the prepared probe uses (0 or 1; needs
  * cyc_probe_prepare). */
 int cyc_set_option(cyc_ctx* ctx, const char* name, int64_t value);
 int cyc_get_option(cyc_ctx* ctx, const char* name, int64_t* value);

@@ -150,18 +150,19 @@ def first_pods(tpl_of, n_templates):
     return first
 
 
-def template_rows(oracle, probes, pods, base_of):
+def template_rows(oracle, probes, pods, base_of, bases=BASE):
     """Oracle rows and status of `pods` for every base probe: (R_in[n,B,W], R_eg[n,B,W] u64, S[n,B] u8);
-    a base probe no slot uses keeps zero rows."""
+    a base probe no slot uses keeps zero rows.  `bases`: the probe list base_of indexes (a problem may
+    bring its own)."""
     P, K = oracle.shape(probes)
     assert K == len(base_of), (K, len(base_of))
     W = (P + 63) // 64
     slot_of = {}
     for k, b in enumerate(base_of):
         slot_of.setdefault(int(b), k)
-    R_in = np.zeros((len(pods), len(BASE), W), np.uint64)
-    R_eg = np.zeros((len(pods), len(BASE), W), np.uint64)
-    S = np.zeros((len(pods), len(BASE)), np.uint8)
+    R_in = np.zeros((len(pods), len(bases), W), np.uint64)
+    R_eg = np.zeros((len(pods), len(bases), W), np.uint64)
+    S = np.zeros((len(pods), len(bases)), np.uint8)
     for i, pod in enumerate(pods):
         for b, k in slot_of.items():
             R_in[i, b] = oracle.row(probes, "ingress", int(pod), k, threads=16)
