@@ -53,6 +53,8 @@ EXPORTS = [
     "cyc_table_run",
     "cyc_table_wrap",
     "cyc_table_cells",
+    "cyc_table_counts",
+    "cyc_table_compare",
     "cyc_table_shape",
     "cyc_table_error",
     "cyc_table_destroy",
@@ -150,6 +152,8 @@ def lib():
         L.cyc_table_run.argtypes = [vp, i64, i64, ctypes.POINTER(vp)]
         L.cyc_table_wrap.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(vp)]
         L.cyc_table_cells.argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]
+        L.cyc_table_counts.argtypes = [vp, i64, i64, vp, vp, vp, vp]
+        L.cyc_table_compare.argtypes = [vp, vp, i64, i64, i, vp, vp, vp, vp]
         L.cyc_table_shape.argtypes = [vp, ctypes.POINTER(i64), i]
         L.cyc_table_error.argtypes = [vp]
         L.cyc_table_error.restype = cp

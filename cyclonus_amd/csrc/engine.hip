@@ -57,6 +57,7 @@
 #include "dev_emit.hpp"
 #include "dev_query.hpp"
 #include "dev_gather.hpp"
+#include "dev_table.hpp"
 
 // Host side: context, planner, enqueueing; the C ABI below
 #include "ctx.hpp"
@@ -570,6 +571,202 @@ int cyc_table_cells(cyc_table* t, int64_t s_lo, int64_t s_hi, int64_t d_lo, int6
     return (int)CYC_ERR_OOM;
   }
   return (int)CYC_OK;
+}
+
+// ---------------------------------------------------------------- whole-table counts and comparison
+// Failures of the table entry points land in cyc_table_error(t), as cyc_table_cells' do.
+static int table_guarded(cyc_table* t, const std::function<int()>& f) {
+  try {
+    return f();
+  } catch (HipErr& h) {
+    t->err = h.msg;
+    return (int)CYC_ERR_HIP;
+  } catch (std::bad_alloc&) {
+    t->err = "host allocation failed";
+    return (int)CYC_ERR_OOM;
+  }
+}
+
+static bool table_whole(const cyc_table* t) {
+  return t->partition == CYC_ROWS_SOURCE || (t->row_lo == 0 && t->row_hi == int64_t(t->P));
+}
+
+// The tile kernel's view of a whole target-row table (sources [0, P)) or of a source-row table.
+static TileArgs tile_args(const cyc_table* t, int64_t k_lo, int64_t k_hi) {
+  TileArgs a{};
+  a.P = t->P, a.K = t->K, a.W = t->W;
+  a.WA = t->wa, a.w0 = t->w0;
+  a.s_lo = uint32_t(t->row_lo), a.s_hi = uint32_t(t->row_hi);
+  a.k_lo = uint32_t(k_lo), a.nk = uint32_t(k_hi - k_lo);
+  a.a = TablePlanes{t->in, t->eg, t->status};
+  return a;
+}
+
+static dim3 tile_grid(const cyc_table* t) { return dim3((t->W + TT_WORDS - 1) / TT_WORDS, (t->wa + TT_WORDS - 1) / TT_WORDS); }
+
+int cyc_table_counts(cyc_table* t, int64_t k_lo, int64_t k_hi, int64_t* ingress, int64_t* egress, int64_t* combined,
+                     int64_t* no_job) {
+  if (!t) return CYC_ERR_ARG;
+  auto bad = [&](const char* m) {
+    t->err = m;
+    return (int)CYC_ERR_ARG;
+  };
+  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
+  if (!ingress && !egress && !combined && !no_job) return bad("no output requested");
+  const bool whole = table_whole(t);
+  // a partial target-row table holds the ingress rows of its destinations and the egress rows of its
+  // sources: no cell has both
+  if (!whole && (combined || no_job)) return bad("ingress cells need destinations inside the table's rows");
+  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
+  for (int64_t i = 0; i < nk * 6; i++) {
+    if (ingress) ingress[i] = 0;
+    if (egress) egress[i] = 0;
+    if (combined) combined[i] = 0;
+  }
+  if (no_job) *no_job = 0;
+  if (!nk || !P) return (int)CYC_OK;
+  return table_guarded(t, [&]() -> int {
+    DeviceGuard dg(t->device);
+    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    // allowed cells per (row, slot): whole tables [nk][3][P] by destination (Ingress, Egress, Combined);
+    // partial ones [rows][nk][2] (Ingress of destination row r, Egress of source row r)
+    const int per = whole ? 3 : 2;
+    const uint64_t n_cnt = uint64_t(whole ? P : rows) * nk * per;
+    std::vector<unsigned long long> cnt(n_cnt, 0);
+    std::vector<uint8_t> st(size_t(P) * K);
+    DevBuf d_cnt, d_valid;
+    if (n_cnt) {
+      d_cnt.alloc(n_cnt * 8);
+      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
+    }
+    if (whole && rows) {
+      TileArgs a = tile_args(t, k_lo, k_hi);
+      a.cnt = d_cnt.as<unsigned long long>();
+      k_table_tiles<false><<<tile_grid(t), 1024, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+    } else if (rows) {
+      RowCountArgs a{};
+      a.P = t->P, a.K = t->K, a.W = t->W, a.row_lo = uint32_t(t->row_lo), a.rows = uint32_t(rows);
+      a.k_lo = uint32_t(k_lo), a.nk = uint32_t(nk);
+      a.t = TablePlanes{t->in, t->eg, t->status};
+      d_valid.alloc(uint64_t(nk) * t->W * 8);
+      a.valid = d_valid.as<uint64_t>();
+      a.cnt = d_cnt.as<unsigned long long>();
+      k_table_valid_words<<<grid1(uint64_t(nk) * t->W, 256), 256, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+      k_table_row_counts<<<unsigned((uint64_t(rows) * nk + 3) / 4), 256, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+    }
+    if (n_cnt) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipMemcpyAsync(st.data(), t->status, st.size(), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    // the status-only terms (jobrunner.go:36-55): a BadPortProtocol / BadNamedPort job is one code for
+    // every source of the destination, Egress unknown; a slot without a job is CYC_CONN_NO_JOB
+    const int64_t n_src = whole ? rows : P;  // sources of an ingress row's cells
+    for (int64_t kk = 0; kk < nk; kk++) {
+      int64_t* oi = ingress ? ingress + kk * 6 : nullptr;
+      int64_t* oe = egress ? egress + kk * 6 : nullptr;
+      int64_t* oc = combined ? combined + kk * 6 : nullptr;
+      // ingress (and combined) over the destinations the table answers; egress over every destination
+      for (int64_t d = 0; d < P; d++) {
+        const uint8_t s = st[size_t(d * K + k_lo + kk)];
+        const bool in_rows = whole || (d >= t->row_lo && d < t->row_hi);
+        const int inv = s == CYC_JOB_BAD_PORT_PROTOCOL ? CYC_CONN_INVALID_PORT_PROTOCOL : CYC_CONN_INVALID_NAMED_PORT;
+        if (s == CYC_JOB_VALID) {
+          if (whole) {
+            const unsigned long long* c = &cnt[size_t(kk * 3 * P + d)];
+            if (oi) oi[CYC_CONN_ALLOWED] += int64_t(c[0]), oi[CYC_CONN_BLOCKED] += rows - int64_t(c[0]);
+            if (oe) oe[CYC_CONN_ALLOWED] += int64_t(c[P]), oe[CYC_CONN_BLOCKED] += rows - int64_t(c[P]);
+            if (oc) oc[CYC_CONN_ALLOWED] += int64_t(c[2 * P]), oc[CYC_CONN_BLOCKED] += rows - int64_t(c[2 * P]);
+          } else {
+            if (oi && in_rows) {
+              const int64_t c = int64_t(cnt[size_t(((d - t->row_lo) * nk + kk) * 2)]);
+              oi[CYC_CONN_ALLOWED] += c, oi[CYC_CONN_BLOCKED] += n_src - c;
+            }
+            if (oe) oe[CYC_CONN_BLOCKED] += rows;  // (the allowed ones move over below)
+          }
+        } else if (s == CYC_JOB_NONE) {
+          if (no_job) *no_job += rows;
+        } else {
+          if (oi && in_rows) oi[inv] += n_src;
+          if (oc) oc[inv] += rows;
+          if (oe) oe[CYC_CONN_UNKNOWN] += rows;
+        }
+      }
+      if (!whole && oe)
+        for (int64_t r = 0; r < rows; r++) {
+          const int64_t c = int64_t(cnt[size_t((r * nk + kk) * 2 + 1)]);
+          oe[CYC_CONN_ALLOWED] += c, oe[CYC_CONN_BLOCKED] -= c;
+        }
+    }
+    return (int)CYC_OK;
+  });
+}
+
+int cyc_table_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t pair_counts[3],
+                      int64_t* slot_counts, int64_t* dst_counts, uint64_t* d_diff) {
+  if (!ta) return CYC_ERR_ARG;
+  cyc_table* t = ta;
+  auto bad = [&](const char* m) {
+    t->err = m;
+    return (int)CYC_ERR_ARG;
+  };
+  if (!tb) return bad("null table");
+  if (!pair_counts) return bad("null pair_counts");
+  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition ||
+      ta->row_lo != tb->row_lo || ta->row_hi != tb->row_hi)
+    return bad("cannot compare tables of different devices, shapes, partitions or rows");
+  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
+  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
+  if (reinterpret_cast<uintptr_t>(d_diff) % 8) return bad("d_diff is not 8-byte aligned");
+  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
+  return table_guarded(t, [&]() -> int {
+    DeviceGuard dg(t->device);
+    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    const uint64_t per = uint64_t(nk) + 2, n_cnt = uint64_t(P) * per;
+    std::vector<unsigned long long> cnt(n_cnt, 0);
+    std::vector<uint8_t> sa(size_t(P) * K), sb(size_t(P) * K);
+    if (P && rows) {
+      DevBuf d_cnt;
+      d_cnt.alloc(n_cnt * 8);
+      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
+      TileArgs a = tile_args(t, k_lo, k_hi);
+      a.b = TablePlanes{tb->in, tb->eg, tb->status};
+      a.ignore_loopback = ignore_loopback ? 1u : 0u;
+      a.cnt = d_cnt.as<unsigned long long>();
+      a.diff = d_diff;
+      k_table_tiles<true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipMemcpyAsync(sa.data(), ta->status, sa.size(), hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipMemcpyAsync(sb.data(), tb->status, sb.size(), hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipStreamSynchronize(t->stream));  // (d_cnt is freed after it)
+    }
+    // ValueCounts (comparisontable.go:109-123): a pair is the Items' equalsDict (:26-36) unless it is an
+    // ignored loopback; the table answers the pairs (s in its rows, every d)
+    int64_t differ = 0, self_differ = 0;
+    for (int64_t d = 0; d < P; d++) differ += int64_t(cnt[size_t(nk * P + d)]), self_differ += int64_t(cnt[size_t((nk + 1) * P + d)]);
+    pair_counts[2] = ignore_loopback ? rows : 0;
+    pair_counts[1] = differ - (ignore_loopback ? self_differ : 0);
+    pair_counts[0] = rows * P - pair_counts[1] - pair_counts[2];
+    // per job (ValueCountsByProtocol :89-107, ResultsByProtocol :14-20,69-79): every cell whose job a holds
+    for (int64_t i = 0; slot_counts && i < nk * 3; i++) slot_counts[i] = 0;
+    if (slot_counts || dst_counts)
+      for (int64_t d = 0; d < P; d++)
+        for (int64_t kk = 0; kk < nk; kk++) {
+          int64_t v[3] = {0, 0, 0};
+          if (sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE) {
+            v[2] = ignore_loopback && d >= t->row_lo && d < t->row_hi ? 1 : 0;
+            v[1] = int64_t(cnt[size_t(kk * P + d)]);
+            v[0] = rows - v[1] - v[2];
+          }
+          for (int x = 0; x < 3; x++) {
+            if (slot_counts) slot_counts[kk * 3 + x] += v[x];
+            if (dst_counts) dst_counts[(d * nk + kk) * 3 + x] = v[x];
+          }
+        }
+    return (int)CYC_OK;
+  });
 }
 
 void cyc_table_destroy(cyc_table* t) {

@@ -154,7 +154,7 @@ class Engine:
         hi = self.shape["pods"] if row_hi is None else row_hi
         t = ctypes.c_void_p()
         check(self._ctx, lib().cyc_table_run_rows(self._ctx, _lib.PARTITIONS[partition], int(row_lo), int(hi), ctypes.byref(t)))
-        return DeviceTable(t)
+        return DeviceTable(t, self.device)
 
     def wrap_table(self, d_ingress: int, d_egress: int, d_status: int, row_lo: int = 0, row_hi=None,
                    partition: str = "target") -> "DeviceTable":
@@ -164,7 +164,7 @@ class Engine:
         check(self._ctx, lib().cyc_table_wrap_rows(self._ctx, ctypes.c_void_p(d_ingress), ctypes.c_void_p(d_egress),
                                                    ctypes.c_void_p(d_status), _lib.PARTITIONS[partition], int(row_lo), int(hi),
                                                    ctypes.byref(t)))
-        return DeviceTable(t)
+        return DeviceTable(t, self.device)
 
     # ---------------------------------------------------------------- multi-GPU assembly (RCCL, comm.hpp)
     @staticmethod
@@ -203,7 +203,7 @@ class Engine:
         """cyc_table_allgather (collective): a whole device table from this rank's shard table."""
         t = ctypes.c_void_p()
         check(self._ctx, lib().cyc_table_allgather(self._ctx, shard._t, ctypes.byref(t)))
-        return DeviceTable(t)
+        return DeviceTable(t, self.device)
 
     def merge_sources(self, d_slices, d_ingress_full: int, stream: int = 0):
         """cyc_rows_merge_sources: every source shard's ingress slices (device pointers, rank order) ->
@@ -304,10 +304,12 @@ class Engine:
 
 
 class DeviceTable:
-    """A cyc_table: verdict planes resident on the GPU; cells() returns probe.Connectivity codes."""
+    """A cyc_table: verdict planes resident on the GPU; cells() returns probe.Connectivity codes, counts()
+    and compare() the whole-table summaries (computed on the device)."""
 
-    def __init__(self, handle: ctypes.c_void_p):
+    def __init__(self, handle: ctypes.c_void_p, device: int = 0):
         self._t = handle
+        self.device = device  # HIP ordinal of the GPU the planes live on
         v = (ctypes.c_int64 * 8)()
         lib().cyc_table_shape(self._t, v, 8)
         self.pods, self.slots, self.words, self.row_lo, self.row_hi = (int(x) for x in v[:5])
@@ -334,4 +336,41 @@ class DeviceTable:
         rc = lib().cyc_table_cells(self._t, int(s_lo), int(s_hi), int(d_lo), int(d_hi), int(k_lo), int(k_hi), *ptr)
         if rc != _lib.OK:
             raise _lib.CyclonusError(rc, lib().cyc_table_error(self._t).decode(errors="replace"))
+        return out
+
+    def _check(self, rc):
+        if rc != _lib.OK:
+            raise _lib.CyclonusError(rc, lib().cyc_table_error(self._t).decode(errors="replace"))
+
+    def counts(self, k_lo=0, k_hi=None, want=("ingress", "egress", "combined", "no_job")):
+        """cyc_table_counts: {name: i64 [k, 6]} cells per cyc_connectivity code of slots [k_lo, k_hi) over every
+        cell the table answers, and "no_job": the cells without a job."""
+        k_hi = self.slots if k_hi is None else k_hi
+        out = {n: np.zeros((max(k_hi - k_lo, 0), 6), np.int64) for n in want if n != "no_job"}
+        nj = ctypes.c_int64(0)
+        ptr = [out[n].ctypes.data if n in out else None for n in ("ingress", "egress", "combined")]
+        self._check(lib().cyc_table_counts(self._t, int(k_lo), int(k_hi), *ptr, ctypes.byref(nj) if "no_job" in want else None))
+        if "no_job" in want:
+            out["no_job"] = int(nj.value)
+        return out
+
+    def compare(self, other: "DeviceTable", k_lo=0, k_hi=None, ignore_loopback=False, want_diff=False, d_diff=None):
+        """cyc_table_compare(self, other): {"pairs": i64 [3], "slots": i64 [k, 3], "dst": i64 [P, k, 3]} in
+        (same, different, ignored) order, and with want_diff "diff": a torch int64 tensor [P, window words] on the
+        table's device, row d bit s set iff the Items (s, d) differ (d_diff: a device pointer to write that plane
+        to instead)."""
+        k_hi = self.slots if k_hi is None else k_hi
+        nk = max(k_hi - k_lo, 0)
+        out = {"pairs": np.zeros(3, np.int64), "slots": np.zeros((nk, 3), np.int64), "dst": np.zeros((self.pods, nk, 3), np.int64)}
+        diff = None
+        if want_diff:
+            import torch
+
+            diff = torch.empty((self.pods, self.window[1] if self.partition == "source" else self.words), dtype=torch.int64,
+                               device=f"cuda:{self.device}")
+        self._check(lib().cyc_table_compare(self._t, other._t, int(k_lo), int(k_hi), int(bool(ignore_loopback)),
+                                            out["pairs"].ctypes.data, out["slots"].ctypes.data, out["dst"].ctypes.data,
+                                            ctypes.c_void_p(d_diff or (diff.data_ptr() if want_diff and diff.numel() else None))))
+        if want_diff:
+            out["diff"] = diff
         return out

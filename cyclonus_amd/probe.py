@@ -156,6 +156,59 @@ class PlaneCells:
                "combined": np.where(valid, allowed(ai & ae), inv)}
         return {n: np.broadcast_to(out[n], (s_hi - s_lo, d_hi - d_lo, k_hi - k_lo)).astype(np.uint8) for n in want}
 
+    # The whole-table consumers, cell by cell (the restatement cyc_table_counts / cyc_table_compare are
+    # tested against; sources go through in chunks so the code arrays stay small).
+    SOURCE_CHUNK = 64
+
+    def _source_chunks(self):
+        P = self.status.shape[0]
+        return P, [(lo, min(lo + self.SOURCE_CHUNK, P)) for lo in range(0, P, self.SOURCE_CHUNK)]
+
+    def counts(self, k_lo=0, k_hi=None, want=("ingress", "egress", "combined", "no_job")):
+        """cyc_table_counts: {name: i64 [k, 6]} cells per Connectivity code, "no_job": cells without a job."""
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        P, chunks = self._source_chunks()
+        out = {n: np.zeros((max(k_hi - k_lo, 0), 6), np.int64) for n in ("ingress", "egress", "combined")}
+        no_job = 0
+        for lo, hi in chunks:
+            cells = self.cells(lo, hi, 0, P, k_lo, k_hi)
+            for n, codes in cells.items():
+                for c in range(6):
+                    out[n][:, c] += (codes == c).sum(axis=(0, 1))
+            no_job += int((cells["combined"] == _lib.CONN_NO_JOB).sum())
+        out["no_job"] = no_job
+        return {n: out[n] for n in want}
+
+    def compare(self, other, k_lo=0, k_hi=None, ignore_loopback=False, want_diff=False):
+        """cyc_table_compare(self, other): Combined of self (the kube probe) against Combined of other:
+        {"pairs": [3], "slots": [k, 3], "dst": [P, k, 3]} in (same, different, ignored) order
+        (comparisontable.go:14-36,89-123), with want_diff "diff": u64 [P, W], row d bit s = the Items (s, d) differ."""
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        P, chunks = self._source_chunks()
+        if other.status.shape != self.status.shape:
+            raise ValueError("cannot compare tables of different shapes")
+        nk = max(k_hi - k_lo, 0)
+        pairs, dst = np.zeros(3, np.int64), np.zeros((P, nk, 3), np.int64)
+        diff = np.zeros((P, (P + 63) // 64), np.uint64)
+        for lo, hi in chunks:
+            ca = self.cells(lo, hi, 0, P, k_lo, k_hi, want=("combined",))["combined"]
+            cb = other.cells(lo, hi, 0, P, k_lo, k_hi, want=("combined",))["combined"]
+            loopback = (np.arange(lo, hi)[:, None] == np.arange(P)[None, :]) & bool(ignore_loopback)
+            job = ca != _lib.CONN_NO_JOB  # every job of the kube Item, once
+            ignored = job & loopback[:, :, None]
+            same = job & ~ignored & (ca == cb)
+            different = job & ~ignored & (ca != cb)  # (a job the other table lacks included)
+            for x, m in enumerate((same, different, ignored)):
+                dst[:, :, x] += m.sum(axis=0)
+            item_differs = (ca != cb).any(axis=2)  # equalsDict over the job keys, NO_JOB included
+            pairs += [int((~loopback & ~item_differs).sum()), int((~loopback & item_differs).sum()), int(loopback.sum())]
+            s, d = np.nonzero(item_differs)
+            np.bitwise_or.at(diff, (d, (s + lo) // 64), np.uint64(1) << ((s + lo) % 64).astype(np.uint64))
+        out = {"pairs": pairs, "slots": dst.sum(axis=0), "dst": dst}
+        if want_diff:
+            out["diff"] = diff
+        return out
+
 
 class Table:
     """Lazy probe.Table over one probe config's slots of a verdict table (table.go:24-56).

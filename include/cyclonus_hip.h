@@ -302,6 +302,42 @@ int cyc_table_wrap_rows(cyc_ctx* ctx, const uint64_t* d_ingress, const uint64_t*
  * sources inside the table's rows (any destination). */
 int cyc_table_cells(cyc_table* t, int64_t s_lo, int64_t s_hi, int64_t d_lo, int64_t d_hi, int64_t k_lo, int64_t k_hi,
                     uint8_t* ingress, uint8_t* egress, uint8_t* combined);
+/* ---- Whole-table consumers, computed where the planes are (synchronous, on the table's own stream
+ * like cyc_table_cells; valid after the context is destroyed).  Both make one pass over the planes of
+ * the slot range (no host copy of a plane); plane bits at or beyond P and bits of non-VALID slots are
+ * ignored (a wrapped plane is the caller's memory).  Accepted tables: a whole target-row table (row_lo = 0, row_hi = P) or a
+ * CYC_ROWS_SOURCE table, which answers the cells (s in its rows, every d, k), so the results of a
+ * partition's shards add up to the whole table's.  Failures: CYC_ERR_ARG with cyc_table_error(t)
+ * (of `a` for cyc_table_compare).
+ *
+ * Connectivity counts of slots [k_lo, k_hi) over every cell the table answers: the Result / Printer
+ * summaries.  out arrays (host, each optional, at least one): [(k - k_lo) * 6 + c] = number of cells
+ * (s, d, k) whose JobResult.Ingress / .Egress / .Combined is cyc_connectivity c (0..5), mapping as
+ * cyc_table_cells (jobrunner.go:36-55,85-93); *no_job (optional) = cells with CYC_CONN_NO_JOB.
+ * A partial target-row table is accepted when combined and no_job are NULL: Ingress is counted over
+ * its destinations (every source), Egress over its sources (every destination). */
+int cyc_table_counts(cyc_table* t, int64_t k_lo, int64_t k_hi, int64_t* ingress, int64_t* egress, int64_t* combined,
+                     int64_t* no_job);
+/* connectivity.NewComparisonTableFrom(a, b) (pkg/connectivity/comparisontable.go:46-67) without
+ * building the Items: Combined of a (the kube probe) against Combined of b (the simulated one), slots
+ * [k_lo, k_hi), a cell's Combined code being cyc_table_cells' (CYC_CONN_NO_JOB included).
+ *   pair_counts[3]  ValueCounts (:109-123): (from, to) pairs that are same, different, ignored.  A pair
+ *                   is same iff the codes agree in every slot of the range, NO_JOB included
+ *                   (Item.IsSuccess = equalsDict :22-36: a job's key depends on (to, slot) only, so equal
+ *                   key sets are equal NO_JOB patterns); ignored iff ignore_loopback and from == to.
+ *   slot_counts     optional host [(k - k_lo) * 3 + {same, different, ignored}]: per job, every cell
+ *                   where a holds a job counted once: ignored when ignore_loopback and s == d (the
+ *                   loopback test comes before success, ValueCountsByProtocol :89-107), else same iff
+ *                   b's code equals a's (Item.ResultsByProtocol :14-20); a job b lacks is different (the
+ *                   reference would dereference nil there).
+ *   dst_counts      optional host [(d * (k_hi - k_lo) + k - k_lo) * 3 + ...]: the same per destination.
+ *   d_diff          optional DEVICE plane [P][W] ([P][Wr] over a source table's ingress window), 8-byte
+ *                   aligned (or CYC_ERR_ARG): RenderSuccessTable's matrix (:125-134) keyed by destination
+ *                   like the ingress plane, row d bit s set iff the Items (s, d) differ; loopback is not
+ *                   special; bits at or beyond P are 0; exactly the plane's bytes are written.
+ * a and b must be on one device with equal P, K, partition and rows; the status planes may differ. */
+int cyc_table_compare(cyc_table* a, cyc_table* b, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t pair_counts[3],
+                      int64_t* slot_counts, int64_t* dst_counts, uint64_t* d_diff);
 /* out[0..7] = pods, slots, words, row_lo, row_hi, partition, ingress window first word, window words */
 int cyc_table_shape(const cyc_table* t, int64_t* out, int n);
 const char* cyc_table_error(const cyc_table* t);

@@ -1,0 +1,120 @@
+"""Config #3's whole table through cyc_table_counts and cyc_table_compare, against a plain read of the same planes.
+
+    python scripts/table_counts_bench.py time [reps=3] [out=FILE]   # the table below, as text and one JSON line
+    python scripts/table_counts_bench.py run counts|compare [n=2]   # n calls of one pass (for a rocprofv3 --pmc run)
+
+In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
+drawn with another seed; then, min over reps of the synchronous calls,
+  counts    cyc_table_counts over every slot (reads both planes once: 20 GB)
+  compare   cyc_table_compare of the two tables with d_diff (reads four planes: 40 GB, writes P x W words)
+  read      the yardstick: torch.sum over the same planes viewed as int64 (20 GB, and 40 GB for the four planes)
+  fill      the box's fill figure, as bench.py measures it: torch's fill kernel over two planes' bytes
+and the ratios counts / read and compare / read, with the achieved GB/s of the algorithmic bytes.
+"""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from cyclonus_amd import synth
+from cyclonus_amd.engine import Engine
+from cyclonus_amd.flat import prepare_flat
+
+mode = sys.argv[1] if len(sys.argv) > 1 else "time"
+pos = [a for a in sys.argv[2:] if "=" not in a]
+kw = dict(a.split("=") for a in sys.argv[2:] if "=" in a)
+reps, n_run, config = int(kw.get("reps", 3)), int(kw.get("n", 2)), kw.get("config", "config3")
+SEED_B = 20250218  # the second table's policy seed (synth's own is 20250217)
+
+data = synth.CONFIGS[config]()
+pols_b = synth.CONFIGS[config](seed=SEED_B)["policies"]
+tables, planes = [], []
+for pols in (data["policies"], pols_b):
+    eng = Engine(0)
+    sh = prepare_flat(eng, pols, data["resources"], data["probes"])
+    P, K, W = sh["pods"], sh["slots"], sh["words"]
+    d_in = torch.empty((P, K, W), dtype=torch.int64, device="cuda")
+    d_eg = torch.empty((P, K, W), dtype=torch.int64, device="cuda")
+    d_st = torch.empty((P, K), dtype=torch.uint8, device="cuda")
+    eng.run_device(d_in.data_ptr(), d_eg.data_ptr(), d_st.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    tables.append(eng.wrap_table(d_in.data_ptr(), d_eg.data_ptr(), d_st.data_ptr()))
+    planes.append((d_in, d_eg, d_st))
+    eng.close()  # (a table outlives its context; the front's scratch goes)
+ta, tb = tables
+plane_gb = P * K * W * 8 / 1e9
+diff = torch.empty((P, W), dtype=torch.int64, device="cuda")
+
+
+def timed(f, n):
+    best = float("inf")
+    for _ in range(n):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t)
+    return best * 1e3
+
+
+def read(n_tables):
+    return sum(int(torch.sum(p)) for t in planes[:n_tables] for p in t[:2])
+
+
+def fill_gbs():
+    """The box's fill figure (bench.py's write ceiling): torch's fill kernel over two planes' bytes."""
+    scratch = torch.empty_like(planes[0][0])
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for _ in range(3):
+        e0.record()
+        scratch.fill_(0)
+        scratch.fill_(0)
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return 2 * scratch.numel() * 8 / (min(ms) * 1e-3) / 1e9
+
+
+if mode == "run":
+    f = (lambda: ta.counts()) if pos[0] == "counts" else (lambda: ta.compare(tb, d_diff=diff.data_ptr()))
+    for _ in range(n_run):
+        f()
+    sys.exit(0)
+
+c = ta.counts()
+r = ta.compare(tb, ignore_loopback=True, d_diff=diff.data_ptr())
+res = {
+    "config": config, "pods": P, "slots": K, "words": W, "plane_gb": round(plane_gb, 3),
+    "counts_ms": timed(lambda: ta.counts(), reps),
+    "compare_ms": timed(lambda: ta.compare(tb, ignore_loopback=True, d_diff=diff.data_ptr()), reps),
+    "compare_nodiff_ms": timed(lambda: ta.compare(tb, ignore_loopback=True), reps),
+    "read2_ms": timed(lambda: read(1), reps), "read4_ms": timed(lambda: read(2), reps),
+    "combined_allowed": int(c["combined"][:, 5].sum()), "combined_blocked": int(c["combined"][:, 4].sum()), "no_job": c["no_job"],
+    "pairs_same_different_ignored": [int(x) for x in r["pairs"]],
+}
+res["fill_gbs"] = fill_gbs()
+res["counts_over_read"] = res["counts_ms"] / res["read2_ms"]
+res["compare_over_read"] = res["compare_ms"] / res["read4_ms"]
+res["counts_gbs"] = 2 * plane_gb / res["counts_ms"] * 1e3
+res["compare_gbs"] = (4 * plane_gb + P * W * 8 / 1e9) / res["compare_ms"] * 1e3
+res["read2_gbs"] = 2 * plane_gb / res["read2_ms"] * 1e3
+res["read4_gbs"] = 4 * plane_gb / res["read4_ms"] * 1e3
+lines = [
+    f"# {config}: P {P}, K {K}, W {W}; a plane is {plane_gb:.2f} GB; min of {reps} synchronous calls; the box's fill figure {res['fill_gbs']:.0f} GB/s",
+    f"counts   {res['counts_ms']:9.2f} ms  {res['counts_gbs']:7.0f} GB/s of 2 planes   read of 2 planes {res['read2_ms']:9.2f} ms "
+    f"{res['read2_gbs']:7.0f} GB/s   ratio {res['counts_over_read']:.2f}",
+    f"compare  {res['compare_ms']:9.2f} ms  {res['compare_gbs']:7.0f} GB/s of 4 planes + d_diff   read of 4 planes {res['read4_ms']:9.2f} ms "
+    f"{res['read4_gbs']:7.0f} GB/s   ratio {res['compare_over_read']:.2f}   (without d_diff {res['compare_nodiff_ms']:.2f} ms)",
+    f"Combined allowed {res['combined_allowed']}, blocked {res['combined_blocked']}, cells without a job {res['no_job']}; "
+    f"pairs same / different / ignored {res['pairs_same_different_ignored']}",
+    json.dumps(res),
+]
+print("\n".join(lines))
+if "out" in kw:
+    os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
+    with open(kw["out"], "w") as f:
+        f.write("\n".join(lines) + "\n")
