@@ -55,6 +55,8 @@ EXPORTS = [
     "cyc_table_cells",
     "cyc_table_counts",
     "cyc_table_compare",
+    "cyc_table_find",
+    "cyc_table_compare_find",
     "cyc_table_shape",
     "cyc_table_error",
     "cyc_table_destroy",
@@ -90,6 +92,11 @@ ROWS_TARGET, ROWS_SOURCE = 0, 1
 PARTITIONS = {"target": ROWS_TARGET, "source": ROWS_SOURCE}
 
 
+# cyc_view (cyc_table_find)
+VIEW_INGRESS, VIEW_EGRESS, VIEW_COMBINED = 0, 1, 2
+VIEWS = {"ingress": VIEW_INGRESS, "egress": VIEW_EGRESS, "combined": VIEW_COMBINED}
+
+
 class CyclonusError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[cyc_status {code}] {msg}")
@@ -110,6 +117,36 @@ class ProbeShape(ctypes.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class Cell(ctypes.Structure):
+    """cyc_cell: one record of cyc_table_find / cyc_table_compare_find (16 bytes)."""
+    _fields_ = [("s", ctypes.c_uint32), ("d", ctypes.c_uint32), ("k", ctypes.c_uint32),
+                ("ingress", ctypes.c_uint8), ("egress", ctypes.c_uint8), ("combined", ctypes.c_uint8), ("other", ctypes.c_uint8)]
+
+
+# the same record as a numpy structured dtype (what DeviceTable.find and PlaneCells.find return)
+CELL_DTYPE = [("s", "<u4"), ("d", "<u4"), ("k", "<u4"), ("ingress", "u1"), ("egress", "u1"), ("combined", "u1"), ("other", "u1")]
+
+
+def code_mask(codes) -> int:
+    """The code_mask of cyc_table_find for one cyc_connectivity code or several."""
+    mask = 0
+    for c in (codes,) if isinstance(codes, int) else codes:
+        if not 0 <= int(c) < 32:
+            raise ValueError(f"not a cyc_connectivity code: {c}")
+        mask |= 1 << int(c)
+    return mask
+
+
+def pages(page, s_from, s_end):
+    """Yield the records of page(s_from) -> (records, s_next, total) until s_next reaches s_end."""
+    while s_from < s_end:
+        recs, s_next, _ = page(s_from)
+        if s_next <= s_from:
+            raise ValueError("a listing page made no progress (a count-only cap?)")
+        s_from = s_next
+        yield recs
 
 
 _lib = None
@@ -154,6 +191,9 @@ def lib():
         L.cyc_table_cells.argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]
         L.cyc_table_counts.argtypes = [vp, i64, i64, vp, vp, vp, vp]
         L.cyc_table_compare.argtypes = [vp, vp, i64, i64, i, vp, vp, vp, vp]
+        pi64 = ctypes.POINTER(i64)
+        L.cyc_table_find.argtypes = [vp, i, ctypes.c_uint32, i64, i64, i64, vp, i64, pi64, pi64, pi64]
+        L.cyc_table_compare_find.argtypes = [vp, vp, i64, i64, i, i64, vp, i64, pi64, pi64, pi64]
         L.cyc_table_shape.argtypes = [vp, ctypes.POINTER(i64), i]
         L.cyc_table_error.argtypes = [vp]
         L.cyc_table_error.restype = cp

@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import CyclonusPanic
-from .probe import Table
+from .probe import _CONN, Table
 from .tablewriter import render
 
 # comparisontable.go:136-155
@@ -97,6 +97,21 @@ class ComparisonTable:
                 raise CyclonusPanic(0, "assignment to entry in nil map")
             counts[p] = {c: int(n) for c, n in zip(COMPARISONS, v) if n}
         return counts
+
+    def different_jobs(self, ignore_loopback: bool, limit=None):
+        """Yield (from, to, job key, kube Combined, simulated Combined) for every job counted as `different`
+        (Item.ResultsByProtocol :14-20 under the loopback rule of :89-107), at most `limit` of them, in plane order
+        (pod order, then job slots).  The simulated value is None where the simulated table lacks the job.  The
+        cells sources list them (`compare_find`: cyc_table_compare_find on the device for DeviceTables)."""
+        k, pods, n = self.kube.slots, self.kube.resources.pods, 0
+        for page in self.kube.src.compare_find_all(self.simulated.src, k.start, k.stop, bool(ignore_loopback)):
+            for r in page:
+                if limit is not None and n >= limit:
+                    return
+                d, other = int(r["d"]), int(r["other"])
+                yield (pods[int(r["s"])].pod_string(), pods[d].pod_string(), self.kube._job_key(d, int(r["k"]) - k.start),
+                       _CONN[int(r["combined"])], _CONN.get(other))
+                n += 1
 
     def differs(self) -> np.ndarray:
         """bool [P, P] in plane order: [s, d] = not Item(s, d).IsSuccess() (:22-36)."""

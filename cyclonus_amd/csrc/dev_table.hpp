@@ -213,4 +213,221 @@ __global__ __launch_bounds__(256) void k_table_row_counts(RowCountArgs a) {
   if (lane == 0) a.cnt[item * 2] = ni, a.cnt[item * 2 + 1] = ne;
 }
 
+// ---- Which cells: the listing behind a count (cyc_table_find, cyc_table_compare_find).  The records come in
+// (s, d, k) order, source-major like the reference's jobs (resources.go:284-364), so these kernels are the
+// mirror image of k_table_tiles: lane = source.  A wave holds 64 sources of one source word; its own words are
+// the egress words of its row (bits over d, contiguous in the row) and the ingress tile (lane = d, bits over s)
+// comes into that orientation through transpose64.  The status takes part as two bit words over destinations per
+// (slot, destination word), built once by k_find_status_words:
+//   find:     word 0 = VALID, word 1 = the status-only code of the view is in the mask
+//   compare:  word 0 = both VALID, word 1 = a holds a job and the statuses differ
+// so a lane's match word is  word1 | word0 & f(ingress bits, egress bits).
+// Pass 1 (k_table_find_count) counts the matches per (source, block of 16 destination words): every block of
+// the grid owns its counts, plain stores.  k_table_find_scan turns a source's counts into their running sums
+// over the destination blocks and its total; the host's prefix sum over the totals places every source's records
+// and chooses the page.  Pass 2 (k_table_find_emit) is a wave per (source word of the page, destination block that
+// holds a match): a lane starts at its source's place plus the running sum of the block and counts on in a
+// register.  No atomics anywhere, so the order is exact by construction.  Both passes take their match words from
+// find_words, so they cannot disagree about a cell.
+struct FindArgs {
+  TileArgs t;                // (cnt: [n_src] matching cells per source)
+  uint32_t view, code_mask;  // find
+  uint32_t bx0;              // pass 1: the first block of 16 source words (sources before s_from are not asked for)
+  uint32_t NB;               // blocks of 16 destination words
+  uint64_t* stw;             // [nk][W][2] status words
+  uint32_t n_src;            // s_hi - s_lo
+  // [NB][n_src], source-minor (a wave's 512 contiguous bytes): pass 1 the matches of (block, source); after the
+  // scan those of the source's earlier blocks
+  unsigned long long* blk;
+  uint32_t s_from, s_next;   // pass 2: the page's sources
+  const unsigned long long* offs;  // [s_next - s_from + 1] first record of each source of the page, and the end
+  uint4* out;                // the page's records (cyc_cell)
+  uint64_t* scratch;         // [grid][nk][4][64] match and code words when they do not fit the LDS, else null
+};
+
+template <bool CMP>
+__global__ __launch_bounds__(256) void k_find_status_words(FindArgs a) {
+  const TileArgs& t = a.t;
+  const uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x;
+  if (i >= uint64_t(t.nk) * t.W) return;
+  const uint32_t k = t.k_lo + uint32_t(i / t.W), w = uint32_t(i % t.W);
+  uint64_t x = 0, y = 0;
+  for (uint32_t b = 0; b < 64 && w * 64 + b < t.P; b++) {
+    const uint8_t sa = t.a.status[uint64_t(w * 64 + b) * t.K + k];
+    if (CMP) {
+      const uint8_t sb = t.b.status[uint64_t(w * 64 + b) * t.K + k];
+      if (sa == CYC_JOB_VALID && sb == CYC_JOB_VALID) x |= 1ull << b;
+      else if (sa != CYC_JOB_NONE && sa != sb) y |= 1ull << b;
+    } else if (sa == CYC_JOB_VALID) {
+      x |= 1ull << b;
+    } else if (sa != CYC_JOB_NONE) {
+      const uint32_t code = a.view == CYC_VIEW_EGRESS          ? CYC_CONN_UNKNOWN
+                            : sa == CYC_JOB_BAD_PORT_PROTOCOL ? CYC_CONN_INVALID_PORT_PROTOCOL
+                                                              : CYC_CONN_INVALID_NAMED_PORT;
+      if ((a.code_mask >> code) & 1) y |= 1ull << b;
+    }
+  }
+  a.stw[i * 2] = x, a.stw[i * 2 + 1] = y;
+}
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  return uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v >> 32))))) << 32 |
+         uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v))));
+}
+
+// Lane = source 64 * sw + lane, bits over the destinations of word dw, slot k_lo + kk: the match word m, the
+// ingress and egress words of a (i, e) and b's Combined word (o).  ea, eb are the lane's egress words.  Called
+// by whole waves with kk, sw (inside the window) and dw the same in every lane.  ALL: every word is wanted (the
+// records carry every code); otherwise only what m needs is loaded.
+struct FindWords {
+  uint64_t m, i, e, o;
+};
+template <bool CMP, bool ALL>
+__device__ __forceinline__ FindWords find_words(const FindArgs& a, uint32_t kk, uint32_t sw, uint32_t dw, uint32_t lane, bool s_ok,
+                                                uint64_t ea, uint64_t eb) {
+  const TileArgs& t = a.t;
+  const uint64_t* st = a.stw + (uint64_t(kk) * t.W + dw) * 2;
+  const uint64_t w0 = uniform64(st[0]), w1 = uniform64(st[1]);
+  FindWords f{w1, 0, ea, 0};
+  if (ALL || w0) {
+    const uint32_t d = dw * 64 + lane;  // (the ingress loads have lane = d)
+    const bool d_ok = d < t.P;
+    const uint64_t at = (uint64_t(d) * t.K + t.k_lo + kk) * t.WA + (sw - t.w0);
+    if (ALL || CMP || a.view != CYC_VIEW_EGRESS) f.i = transpose64(d_ok ? t.a.in[at] : 0ull, lane);
+    if (CMP) {
+      f.o = transpose64(d_ok ? t.b.in[at] : 0ull, lane) & eb;
+      f.m |= w0 & ((f.i & ea) ^ f.o);
+    } else {
+      const uint64_t x = a.view == CYC_VIEW_INGRESS ? f.i : a.view == CYC_VIEW_EGRESS ? ea : f.i & ea;
+      f.m |= w0 & (((a.code_mask >> CYC_CONN_ALLOWED) & 1 ? x : 0ull) | ((a.code_mask >> CYC_CONN_BLOCKED) & 1 ? ~x : 0ull));
+    }
+  }
+  if (CMP && t.ignore_loopback && sw == dw) f.m &= ~(1ull << lane);
+  if (!s_ok) f.m = 0;
+  return f;
+}
+
+// Pass 1.  A block is 16 waves on 16 neighbouring source words, walking 16 destination words together: a lane's
+// egress words of the block are 128 contiguous bytes of its row, loaded back to back, and the 16 waves' ingress
+// loads of one destination word are the 16 words of the same 64 lines (hence the barrier per step, as in
+// k_table_tiles).  The per-lane sums are the block's own: one store per lane, a wave's 512 contiguous bytes.
+template <bool CMP>
+__global__ __launch_bounds__(1024) void k_table_find_count(FindArgs a) {
+  constexpr uint32_t BATCH = CMP ? TT_BATCH : TT_WORDS;  // (compare holds two tables' words)
+  const TileArgs& t = a.t;
+  const uint32_t lane = threadIdx.x & 63, sw = t.w0 + (a.bx0 + blockIdx.x) * TT_WORDS + (threadIdx.x >> 6);
+  // (a wave past the last source word loads nothing and only keeps the block's barriers)
+  const bool w_ok = sw < t.w0 + t.WA;
+  const uint32_t s = sw * 64 + lane;  // (s >= s_lo = 64 * w0)
+  const bool s_ok = w_ok && s < t.s_hi;
+  const uint32_t dw0 = blockIdx.y * TT_WORDS, dw_end = min(dw0 + TT_WORDS, t.W);
+  uint64_t n = 0;
+  for (uint32_t kk = 0; kk < t.nk; kk++) {
+    const uint64_t eg_at = (uint64_t(s - t.s_lo) * t.K + t.k_lo + kk) * t.W + dw0;
+#pragma unroll 1
+    for (uint32_t h = 0; h < TT_WORDS; h += BATCH) {  // (find: one batch)
+      uint64_t ea[BATCH], eb[BATCH];
+#pragma unroll
+      for (uint32_t j = 0; j < BATCH; j++) {
+        const bool on = s_ok && dw0 + h + j < dw_end;
+        ea[j] = on ? t.a.eg[eg_at + h + j] : 0ull;
+        eb[j] = CMP && on ? t.b.eg[eg_at + h + j] : 0ull;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < BATCH; j++) {
+        const uint32_t dw = dw0 + h + j;
+        if (dw >= dw_end) continue;
+        __syncthreads();  // the block's waves take a step together (its ingress lines)
+        if (w_ok) n += __popcll(find_words<CMP, false>(a, kk, sw, dw, lane, s_ok, ea[j], eb[j]).m);
+      }
+    }
+  }
+  if (s_ok) a.blk[uint64_t(blockIdx.y) * a.n_src + (s - t.s_lo)] = n;
+}
+
+// a thread per source from the first one pass 1 counted
+__global__ __launch_bounds__(256) void k_table_find_scan(FindArgs a) {
+  const uint64_t i = uint64_t(a.bx0) * TT_WORDS * 64 + blockIdx.x * uint64_t(blockDim.x) + threadIdx.x;
+  if (i >= a.n_src) return;
+  unsigned long long run = 0;
+  for (uint32_t by = 0; by < a.NB; by++) {
+    unsigned long long* c = a.blk + uint64_t(by) * a.n_src + i;
+    const unsigned long long n = *c;
+    *c = run;
+    run += n;
+  }
+  a.t.cnt[i] = run;
+}
+
+// Pass 2: a wave per (source word of the page, destination block).  Per destination word the lane's words of
+// every slot go to a lane-private column of the buffer (LDS, or global scratch for many slots); the lane then
+// walks its set destination bits in ascending order and under each the slots, which is the (d, k) order of its
+// records.
+template <bool CMP>
+__global__ __launch_bounds__(64) void k_table_find_emit(FindArgs a) {
+  extern __shared__ uint64_t find_lds[];
+  const TileArgs& t = a.t;
+  const uint32_t lane = threadIdx.x;
+  // word x of slot kk: buf[(kk * 4 + x) * 64]
+  uint64_t* buf = (a.scratch ? a.scratch + uint64_t(blockIdx.x) * t.nk * 256 : find_lds) + lane;
+  const uint32_t sw_lo = a.s_from / 64;
+  const uint64_t items = uint64_t((a.s_next + 63) / 64 - sw_lo) * a.NB;
+  for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const uint32_t sw = sw_lo + uint32_t(item / a.NB), by = uint32_t(item % a.NB);
+    const uint32_t s = sw * 64 + lane;
+    const bool s_ok = s >= a.s_from && s < a.s_next;
+    // the lane's records of this block: [off, end) of the page
+    unsigned long long off = 0, end = 0;
+    if (s_ok) {
+      const uint64_t i = s - t.s_lo;
+      const unsigned long long before = a.blk[uint64_t(by) * a.n_src + i];
+      off = a.offs[s - a.s_from] + before;
+      end = off + (by + 1 < a.NB ? a.blk[uint64_t(by + 1) * a.n_src + i] : t.cnt[i]) - before;
+    }
+    if (__ballot(off != end) == 0) continue;
+    const uint32_t dw_end = min((by + 1) * TT_WORDS, t.W);
+    for (uint32_t dw = by * TT_WORDS; dw < dw_end; dw++) {
+      uint64_t u = 0;
+      for (uint32_t kk = 0; kk < t.nk; kk++) {
+        const uint64_t eg_at = (uint64_t(s - t.s_lo) * t.K + t.k_lo + kk) * t.W + dw;
+        const FindWords f = find_words<CMP, true>(a, kk, sw, dw, lane, s_ok, s_ok ? t.a.eg[eg_at] : 0ull,
+                                                  CMP && s_ok ? t.b.eg[eg_at] : 0ull);
+        uint64_t* o = buf + uint64_t(kk) * 256;
+        o[0] = f.m, o[64] = f.i, o[128] = f.e, o[192] = f.o;
+        u |= f.m;
+      }
+      while (u) {
+        const uint32_t b = uint32_t(__builtin_ctzll(u)), d = dw * 64 + b;
+        u &= u - 1;
+        for (uint32_t kk = 0; kk < t.nk; kk++) {
+          const uint64_t* o = buf + uint64_t(kk) * 256;
+          if (!((o[0] >> b) & 1)) continue;
+          // the codes of cyc_table_cells (dev_query.hpp)
+          const uint32_t k = t.k_lo + kk;
+          const uint8_t sa = t.a.status[uint64_t(d) * t.K + k];
+          const bool ai = (o[64] >> b) & 1, ae = (o[128] >> b) & 1;
+          uint32_t ci, ce = CYC_CONN_UNKNOWN, co = 0;
+          if (sa == CYC_JOB_VALID) {
+            ci = ai ? CYC_CONN_ALLOWED : CYC_CONN_BLOCKED;
+            ce = ae ? CYC_CONN_ALLOWED : CYC_CONN_BLOCKED;
+          } else {
+            ci = sa == CYC_JOB_BAD_PORT_PROTOCOL ? CYC_CONN_INVALID_PORT_PROTOCOL : CYC_CONN_INVALID_NAMED_PORT;
+          }
+          const uint32_t cc = sa == CYC_JOB_VALID ? (ai && ae ? CYC_CONN_ALLOWED : CYC_CONN_BLOCKED) : ci;
+          if (CMP) {
+            const uint8_t sb = t.b.status[uint64_t(d) * t.K + k];
+            co = sb == CYC_JOB_VALID                ? ((o[192] >> b) & 1 ? CYC_CONN_ALLOWED : CYC_CONN_BLOCKED)
+                 : sb == CYC_JOB_BAD_PORT_PROTOCOL ? CYC_CONN_INVALID_PORT_PROTOCOL
+                 : sb == CYC_JOB_BAD_NAMED_PORT    ? CYC_CONN_INVALID_NAMED_PORT
+                                                   : CYC_CONN_NO_JOB;
+          }
+          // (a record past the source's share would mean the planes changed between the passes)
+          if (off < end) a.out[off] = make_uint4(s, d, k, ci | ce << 8 | cc << 16 | co << 24);
+          off++;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace cyc

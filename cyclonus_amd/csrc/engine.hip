@@ -769,6 +769,124 @@ int cyc_table_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, 
   });
 }
 
+// ---------------------------------------------------------------- which cells: find and compare_find
+static_assert(sizeof(cyc_cell) == 16, "cyc_cell is one 16-byte store");
+constexpr uint32_t FIND_LDS_SLOTS = 32;      // 2 KB of words per slot and wave: up to here they fit 64 KB of LDS
+constexpr uint32_t FIND_SCRATCH_GRID = 1024;  // beyond, the words live in global scratch and the grid is capped
+constexpr uint32_t FIND_EMIT_GRID = 1u << 20;  // waves of the emit kernel; further (source word, block) items by stride
+
+// The shared body of the two entry points: tb == nullptr is find (view, code_mask), otherwise compare_find
+// (ignore_loopback).  The callers have checked what only one of them takes.
+static int table_find(cyc_table* t, cyc_table* tb, int view, uint32_t code_mask, int ignore_loopback, int64_t k_lo, int64_t k_hi,
+                      int64_t s_from, cyc_cell* cells, int64_t cap, int64_t* n, int64_t* s_next, int64_t* total) {
+  auto bad = [&](const std::string& m) {
+    t->err = m;
+    return (int)CYC_ERR_ARG;
+  };
+  if (!n || !s_next || !total) return bad("null n, s_next or total");
+  *n = 0, *total = 0, *s_next = s_from;
+  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
+  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
+  if (s_from < t->row_lo || s_from > t->row_hi) return bad("s_from outside the table's rows");
+  if (cap < 0) return bad("negative cap");
+  if (!cells && cap > 0) return bad("null cells");
+  const bool count_only = !cells;
+  const int64_t nk = k_hi - k_lo, rows = t->row_hi - s_from;
+  if (!nk && !count_only) *s_next = t->row_hi;
+  if (!nk || !rows) return (int)CYC_OK;
+  return table_guarded(t, [&]() -> int {
+    DeviceGuard dg(t->device);
+    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    const bool cmp = tb != nullptr;
+    FindArgs a{};
+    a.t = tile_args(t, k_lo, k_hi);
+    if (cmp) a.t.b = TablePlanes{tb->in, tb->eg, tb->status};
+    a.t.ignore_loopback = ignore_loopback ? 1u : 0u;
+    a.view = uint32_t(view), a.code_mask = code_mask;
+    a.NB = (t->W + TT_WORDS - 1) / TT_WORDS;
+    a.bx0 = uint32_t((s_from / 64 - t->w0) / TT_WORDS);
+    // ---- pass 1: matches per (destination block, source), then per source
+    const uint64_t n_src = uint64_t(t->row_hi - t->row_lo), n_stw = uint64_t(nk) * t->W * 2, n_blk = uint64_t(a.NB) * n_src;
+    DevBuf d_cnt, d_stw, d_blk;
+    d_cnt.alloc(n_src * 8), d_stw.alloc(n_stw * 8), d_blk.alloc(n_blk * 8);
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_src * 8, t->stream));  // (the sources before pass 1's first block)
+    a.n_src = uint32_t(n_src);
+    a.t.cnt = d_cnt.as<unsigned long long>();
+    a.stw = d_stw.as<uint64_t>();
+    a.blk = d_blk.as<unsigned long long>();
+    const dim3 grid((t->wa + TT_WORDS - 1) / TT_WORDS - a.bx0, a.NB);
+    if (cmp) {
+      k_find_status_words<true><<<grid1(n_stw / 2, 256), 256, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+      k_table_find_count<true><<<grid, 1024, 0, t->stream>>>(a);
+    } else {
+      k_find_status_words<false><<<grid1(n_stw / 2, 256), 256, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+      k_table_find_count<false><<<grid, 1024, 0, t->stream>>>(a);
+    }
+    HIPCHK(hipGetLastError());
+    k_table_find_scan<<<grid1(n_src - uint64_t(a.bx0) * TT_WORDS * 64, 256), 256, 0, t->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned long long> cnt(n_src);
+    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_src * 8, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    // ---- the page: sources [s_from, s_next) are the longest run whose records fit into cap
+    const unsigned long long* c = cnt.data() + (s_from - t->row_lo);  // c[i]: source s_from + i
+    for (int64_t i = 0; i < rows; i++) *total += int64_t(c[i]);
+    if (count_only) return (int)CYC_OK;
+    std::vector<unsigned long long> offs(1, 0);  // offs[i]: first record of source s_from + i
+    int64_t page = 0;
+    while (page < rows && offs.back() + c[page] <= (unsigned long long)cap) offs.push_back(offs.back() + c[page++]);
+    if (!page)
+      return bad("source " + std::to_string(s_from) + " alone has " + std::to_string(c[0]) + " matching cells, more than cap " +
+                 std::to_string(cap));
+    *s_next = s_from + page;
+    *n = int64_t(offs.back());
+    if (!*n) return (int)CYC_OK;
+    // ---- pass 2: the records of the page
+    DevBuf d_offs, d_out, d_scratch;
+    d_offs.alloc(offs.size() * 8), d_out.alloc(uint64_t(*n) * sizeof(cyc_cell));
+    HIPCHK(hipMemcpyAsync(d_offs.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, t->stream));
+    a.s_from = uint32_t(s_from), a.s_next = uint32_t(*s_next);
+    a.offs = d_offs.as<unsigned long long>();
+    a.out = d_out.as<uint4>();
+    // a wave per (source word of the page, destination block); those without a match leave at once
+    const uint64_t items = uint64_t((*s_next + 63) / 64 - s_from / 64) * a.NB;
+    uint32_t waves = uint32_t(std::min<uint64_t>(items, FIND_EMIT_GRID));
+    size_t lds = size_t(nk) * 4 * 64 * 8;
+    if (nk > FIND_LDS_SLOTS) {
+      waves = std::min(waves, FIND_SCRATCH_GRID);
+      d_scratch.alloc(uint64_t(waves) * lds);
+      a.scratch = d_scratch.as<uint64_t>();
+      lds = 0;
+    }
+    if (cmp) k_table_find_emit<true><<<waves, 64, lds, t->stream>>>(a);
+    else k_table_find_emit<false><<<waves, 64, lds, t->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cells, d_out.p, uint64_t(*n) * sizeof(cyc_cell), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    return (int)CYC_OK;
+  });
+}
+
+int cyc_table_find(cyc_table* t, int view, uint32_t code_mask, int64_t k_lo, int64_t k_hi, int64_t s_from, cyc_cell* cells, int64_t cap,
+                   int64_t* n, int64_t* s_next, int64_t* total) {
+  if (!t) return CYC_ERR_ARG;
+  if (view != CYC_VIEW_INGRESS && view != CYC_VIEW_EGRESS && view != CYC_VIEW_COMBINED) return t->err = "unknown view", (int)CYC_ERR_ARG;
+  if (!code_mask || code_mask >> 6) return t->err = "code_mask must name codes 0..5", (int)CYC_ERR_ARG;
+  return table_find(t, nullptr, view, code_mask, 0, k_lo, k_hi, s_from, cells, cap, n, s_next, total);
+}
+
+int cyc_table_compare_find(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t s_from, cyc_cell* cells,
+                           int64_t cap, int64_t* n, int64_t* s_next, int64_t* total) {
+  if (!ta) return CYC_ERR_ARG;
+  if (!tb) return ta->err = "null table", (int)CYC_ERR_ARG;
+  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition || ta->row_lo != tb->row_lo ||
+      ta->row_hi != tb->row_hi)
+    return ta->err = "cannot compare tables of different devices, shapes, partitions or rows", (int)CYC_ERR_ARG;
+  return table_find(ta, tb, CYC_VIEW_COMBINED, 0, ignore_loopback, k_lo, k_hi, s_from, cells, cap, n, s_next, total);
+}
+
 void cyc_table_destroy(cyc_table* t) {
   if (!t) return;
   DeviceGuard dg(t->device, false);

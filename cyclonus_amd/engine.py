@@ -305,7 +305,8 @@ class Engine:
 
 class DeviceTable:
     """A cyc_table: verdict planes resident on the GPU; cells() returns probe.Connectivity codes, counts()
-    and compare() the whole-table summaries (computed on the device)."""
+    and compare() the whole-table summaries, find() and compare_find() the cells behind them as records in
+    (s, d, k) order (all computed on the device)."""
 
     def __init__(self, handle: ctypes.c_void_p, device: int = 0):
         self._t = handle
@@ -374,3 +375,45 @@ class DeviceTable:
         if want_diff:
             out["diff"] = diff
         return out
+
+    def _find(self, call, k_lo, k_hi, s_from, cap, out):
+        """One page of a listing: (records, s_next, total).  cap None: pods * slots of the range, which always
+        makes progress; cap 0 without `out`: the count-only call.  `out`: a CELL_DTYPE array to write into (cap
+        defaults to its length); the result is a view of its first n records."""
+        k_hi = self.slots if k_hi is None else k_hi
+        s_from = self.row_lo if s_from is None else s_from
+        if cap is None:
+            cap = len(out) if out is not None else max(self.pods * max(k_hi - k_lo, 0), 1)
+        if out is None and cap:
+            out = np.zeros(cap, _lib.CELL_DTYPE)
+        if out is not None and (out.dtype != np.dtype(_lib.CELL_DTYPE) or not out.flags.c_contiguous or len(out) < cap):
+            raise ValueError("out must be a contiguous CELL_DTYPE array of at least cap records")
+        n, s_next, total = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = call(int(k_lo), int(k_hi), int(s_from), ctypes.c_void_p(out.ctypes.data if out is not None else None), int(cap),
+                  ctypes.byref(n), ctypes.byref(s_next), ctypes.byref(total))
+        if rc != _lib.OK:
+            e = _lib.CyclonusError(rc, lib().cyc_table_error(self._t).decode(errors="replace"))
+            e.total = int(total.value)
+            raise e
+        recs = out[:n.value] if out is not None else np.zeros(0, _lib.CELL_DTYPE)
+        return recs, int(s_next.value), int(total.value)
+
+    def find(self, view, codes, k_lo=0, k_hi=None, s_from=None, cap=None, out=None):
+        """cyc_table_find: the cells of slots [k_lo, k_hi) whose Connectivity in `view` ("ingress", "egress",
+        "combined" or a cyc_view) is one of `codes` (cyc_connectivity values), for the sources from s_from on that
+        fit into cap records, in (s, d, k) order -> (records, s_next, total)."""
+        v, mask = _lib.VIEWS.get(view, view), _lib.code_mask(codes)
+        return self._find(lambda k0, k1, *rest: lib().cyc_table_find(self._t, int(v), mask, k0, k1, *rest), k_lo, k_hi, s_from, cap, out)
+
+    def compare_find(self, other: "DeviceTable", k_lo=0, k_hi=None, ignore_loopback=False, s_from=None, cap=None, out=None):
+        """cyc_table_compare_find: the cells cyc_table_compare counts as `different`, listed like find; a record's
+        `other` is the other table's Combined code."""
+        return self._find(lambda k0, k1, *rest: lib().cyc_table_compare_find(self._t, other._t, k0, k1, int(bool(ignore_loopback)), *rest),
+                          k_lo, k_hi, s_from, cap, out)
+
+    def find_all(self, view, codes, k_lo=0, k_hi=None, cap=None):
+        """The pages of find, from the table's first source to its last."""
+        yield from _lib.pages(lambda s: self.find(view, codes, k_lo, k_hi, s, cap), self.row_lo, self.row_hi)
+
+    def compare_find_all(self, other, k_lo=0, k_hi=None, ignore_loopback=False, cap=None):
+        yield from _lib.pages(lambda s: self.compare_find(other, k_lo, k_hi, ignore_loopback, s, cap), self.row_lo, self.row_hi)

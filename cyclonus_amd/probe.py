@@ -209,6 +209,90 @@ class PlaneCells:
             out["diff"] = diff
         return out
 
+    # The listings (cyc_table_find / cyc_table_compare_find), cell by cell: the same contract as
+    # DeviceTable.find / compare_find, which are tested against this restatement.
+    def _page(self, matcher, k_lo, k_hi, s_from, cap):
+        """matcher(lo, hi, k_lo, k_hi) -> (codes {name: [s, d, k]}, match bool [s, d, k], other u8 [s, d, k] or None)
+        for sources [lo, hi).  cap None: pods * slots; cap 0: the count-only call."""
+        P, K = self.status.shape
+        k_hi = K if k_hi is None else k_hi
+        s_from = 0 if s_from is None else s_from
+        if not 0 <= k_lo <= k_hi <= K:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "slot range out of bounds")
+        if not 0 <= s_from <= P:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "s_from outside the table's rows")
+        nk, count_only = k_hi - k_lo, cap == 0
+        cap = max(P * nk, 1) if cap is None else cap
+        if cap < 0:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "negative cap")
+        empty = np.zeros(0, _lib.CELL_DTYPE)
+        if nk == 0:
+            return empty, (s_from if count_only else P), 0
+        pages, n, total, s_next, fits, first = [], 0, 0, s_from, not count_only, 0
+        for lo in range(s_from, P, self.SOURCE_CHUNK):
+            hi = min(lo + self.SOURCE_CHUNK, P)
+            codes, match, other = matcher(lo, hi, k_lo, k_hi)
+            per_source = match.sum(axis=(1, 2))
+            total += int(per_source.sum())
+            if lo == s_from:
+                first = int(per_source[0])
+            if not fits:
+                continue
+            for c in per_source:  # the longest run of sources whose records fit
+                if n + int(c) > cap:
+                    fits = False
+                    break
+                n, s_next = n + int(c), s_next + 1
+            s, d, k = np.nonzero(match[:s_next - lo])  # (row-major: ascending (s, d, k))
+            page = np.zeros(len(s), _lib.CELL_DTYPE)
+            page["s"], page["d"], page["k"] = s + lo, d, k + k_lo
+            for name in ("ingress", "egress", "combined"):
+                page[name] = codes[name][s, d, k]
+            if other is not None:
+                page["other"] = other[s, d, k]
+            pages.append(page)
+        if not count_only and s_next == s_from and s_from < P:
+            e = _lib.CyclonusError(_lib.ERR_ARG, f"source {s_from} alone has {first} matching cells, more than cap {cap}")
+            e.total = total
+            raise e
+        return (np.concatenate(pages) if pages else empty), s_next, total
+
+    def find(self, view, codes, k_lo=0, k_hi=None, s_from=None, cap=None):
+        """cyc_table_find over host planes -> (records, s_next, total)."""
+        view = {v: n for n, v in _lib.VIEWS.items()}.get(view, view)
+        if view not in _lib.VIEWS:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "unknown view")
+        mask = _lib.code_mask(codes)
+        if not mask or mask >> 6:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "code_mask must name codes 0..5")
+        wanted = np.zeros(256, bool)  # (CYC_CONN_NO_JOB is not a job and never matches)
+        wanted[[c for c in range(6) if (mask >> c) & 1]] = True
+        P = self.status.shape[0]
+
+        def matcher(lo, hi, k0, k1):
+            cells = self.cells(lo, hi, 0, P, k0, k1)
+            return cells, wanted[cells[view]], None
+        return self._page(matcher, k_lo, k_hi, s_from, cap)
+
+    def compare_find(self, other, k_lo=0, k_hi=None, ignore_loopback=False, s_from=None, cap=None):
+        """cyc_table_compare_find(self, other) over host planes: the cells compare counts as `different`."""
+        if other.status.shape != self.status.shape:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "cannot compare tables of different devices, shapes, partitions or rows")
+        P = self.status.shape[0]
+
+        def matcher(lo, hi, k0, k1):
+            cells = self.cells(lo, hi, 0, P, k0, k1)
+            ca, cb = cells["combined"], other.cells(lo, hi, 0, P, k0, k1, want=("combined",))["combined"]
+            loopback = (np.arange(lo, hi)[:, None] == np.arange(P)[None, :]) & bool(ignore_loopback)
+            return cells, (ca != _lib.CONN_NO_JOB) & ~loopback[:, :, None] & (ca != cb), cb
+        return self._page(matcher, k_lo, k_hi, s_from, cap)
+
+    def find_all(self, view, codes, k_lo=0, k_hi=None, cap=None):
+        yield from _lib.pages(lambda s: self.find(view, codes, k_lo, k_hi, s, cap), 0, self.status.shape[0])
+
+    def compare_find_all(self, other, k_lo=0, k_hi=None, ignore_loopback=False, cap=None):
+        yield from _lib.pages(lambda s: self.compare_find(other, k_lo, k_hi, ignore_loopback, s, cap), 0, self.status.shape[0])
+
 
 class Table:
     """Lazy probe.Table over one probe config's slots of a verdict table (table.go:24-56).
@@ -269,6 +353,21 @@ class Table:
 
     def keys(self):
         return [(a, b) for a in self.items for b in self.items]
+
+    def find(self, connectivity: str, view: str = "combined"):
+        """Yield (from, to, JobResult) for every job of the table whose Ingress, Egress or Combined (`view`) is
+        `connectivity`, listed by the cells source (cyc_table_find on the device for a DeviceTable).  The order is
+        plane order (the pods as Resources holds them, then the job slots), not the sorted-name order of keys()."""
+        code = next((c for c, name in _CONN.items() if name == connectivity), None)
+        if code is None:
+            raise ValueError(f"invalid Connectivity value: {connectivity}")
+        pods = self.resources.pods
+        for page in self.src.find_all(view, (code,), self.slots.start, self.slots.stop):
+            for r in page:
+                d, j = int(r["d"]), int(r["k"]) - self.slots.start
+                key = self._job_key(d, j)
+                yield (pods[int(r["s"])].pod_string(), pods[d].pod_string(),
+                       JobResult(key, _CONN[int(r["ingress"])], _CONN[int(r["egress"])], _CONN[int(r["combined"])]))
 
     # table.go:58-156
     def render_ingress(self) -> str:

@@ -338,6 +338,38 @@ int cyc_table_counts(cyc_table* t, int64_t k_lo, int64_t k_hi, int64_t* ingress,
  * a and b must be on one device with equal P, K, partition and rows; the status planes may differ. */
 int cyc_table_compare(cyc_table* a, cyc_table* b, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t pair_counts[3],
                       int64_t* slot_counts, int64_t* dst_counts, uint64_t* d_diff);
+/* ---- Which cells: the listing behind a count (the reference walks Wrapped.Keys() and prints whole
+ * tables, printer.go:243-263, comparisontable.go:62-64,125-134; here the answer is a list of the matching
+ * cells).  Accepted tables, stream, lifetime, plane bits at or beyond P and failures: as for
+ * cyc_table_counts / cyc_table_compare above (a partial target-row table is refused). */
+typedef enum { CYC_VIEW_INGRESS = 0, CYC_VIEW_EGRESS = 1, CYC_VIEW_COMBINED = 2 } cyc_view;
+typedef struct {            /* 16 bytes */
+  uint32_t s, d, k;         /* from pod, to pod, slot (plane order) */
+  uint8_t ingress, egress, combined;  /* JobResult of the table (of `a`), cyc_table_cells' codes */
+  uint8_t other;            /* compare: b's Combined code (CYC_CONN_NO_JOB possible); find: 0 */
+} cyc_cell;
+/* The cells (s, d, k), k in [k_lo, k_hi), whose code in `view` (cyc_view) is a cyc_connectivity c in 0..5
+ * with bit c of code_mask set (0, or bits >= 6: CYC_ERR_ARG).  A CYC_CONN_NO_JOB cell is not a job and
+ * never matches; a status-only code (the two invalid kinds, Egress unknown) matches for every source of
+ * that (d, k).
+ * Order and paging: `cells` (host memory, room for `cap` records) receives ALL matching cells of sources
+ * [s_from, *s_next) in ascending (s, d, k) order, *n of them; records at index >= *n are not touched.
+ * *s_next is the largest source <= row_hi for which they fit into cap (it runs over trailing sources
+ * without matches and is row_hi when everything fits); *total = matching cells of sources
+ * [s_from, row_hi).  Continue with s_from = *s_next until it equals row_hi.  cap >= P * (k_hi - k_lo)
+ * always makes progress; if source s_from alone has more matches than cap the call is CYC_ERR_ARG (the
+ * message names the source and its count; *total is still set).  cells == NULL with cap == 0 is a
+ * count-only call: *n = 0, *s_next = s_from, never an error of that kind.  s_from == row_hi: *n = 0,
+ * *total = 0; an empty slot range: *n = 0, *s_next = row_hi, *total = 0.  s_from outside [row_lo, row_hi],
+ * a bad slot range, a negative cap, NULL cells with cap > 0, NULL n, s_next or total: CYC_ERR_ARG.  The
+ * records are the same from run to run. */
+int cyc_table_find(cyc_table* t, int view, uint32_t code_mask, int64_t k_lo, int64_t k_hi, int64_t s_from,
+                   cyc_cell* cells, int64_t cap, int64_t* n, int64_t* s_next, int64_t* total);
+/* The same listing of exactly the cells cyc_table_compare counts as `different` in slot_counts: a holds
+ * a job there, b's Combined code differs from a's (or b lacks the job), and the cell is not an ignored
+ * loopback.  a and b must match as in cyc_table_compare. */
+int cyc_table_compare_find(cyc_table* a, cyc_table* b, int64_t k_lo, int64_t k_hi, int ignore_loopback,
+                           int64_t s_from, cyc_cell* cells, int64_t cap, int64_t* n, int64_t* s_next, int64_t* total);
 /* out[0..7] = pods, slots, words, row_lo, row_hi, partition, ingress window first word, window words */
 int cyc_table_shape(const cyc_table* t, int64_t* out, int n);
 const char* cyc_table_error(const cyc_table* t);

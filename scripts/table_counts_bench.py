@@ -1,7 +1,8 @@
 """Config #3's whole table through cyc_table_counts and cyc_table_compare, against a plain read of the same planes.
 
     python scripts/table_counts_bench.py time [reps=3] [out=FILE]   # the table below, as text and one JSON line
-    python scripts/table_counts_bench.py run counts|compare [n=2]   # n calls of one pass (for a rocprofv3 --pmc run)
+    python scripts/table_counts_bench.py run counts|compare|find_count|compare_find|find_dense [n=2]
+                                                                    # n calls of one pass (for a rocprofv3 --pmc run)
 
 In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
 drawn with another seed; then, min over reps of the synchronous calls,
@@ -9,7 +10,11 @@ drawn with another seed; then, min over reps of the synchronous calls,
   compare   cyc_table_compare of the two tables with d_diff (reads four planes: 40 GB, writes P x W words)
   read      the yardstick: torch.sum over the same planes viewed as int64 (20 GB, and 40 GB for the four planes)
   fill      the box's fill figure, as bench.py measures it: torch's fill kernel over two planes' bytes
-and the ratios counts / read and compare / read, with the achieved GB/s of the algorithmic bytes.
+and the ratios counts / read and compare / read, with the achieved GB/s of the algorithmic bytes.  Then the
+listings (cyc_table_find, cyc_table_compare_find) against counts and compare as their yardsticks:
+  find_count    the count-only calls (pass 1 alone): compare_find of the two tables, find of Combined == blocked
+  compare_find  the sparse case: table A against a torch.clone of its planes with 64 egress bits flipped, in one page
+  find_dense    the dense case: one page of find(Combined == allowed) with cap = P * K
 """
 import json
 import os
@@ -17,9 +22,11 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
 import torch
 
 from cyclonus_amd import synth
+from cyclonus_amd._lib import CELL_DTYPE, CONN_ALLOWED, CONN_BLOCKED
 from cyclonus_amd.engine import Engine
 from cyclonus_amd.flat import prepare_flat
 
@@ -31,7 +38,7 @@ SEED_B = 20250218  # the second table's policy seed (synth's own is 20250217)
 
 data = synth.CONFIGS[config]()
 pols_b = synth.CONFIGS[config](seed=SEED_B)["policies"]
-tables, planes = [], []
+tables, planes, flipped = [], [], []
 for pols in (data["policies"], pols_b):
     eng = Engine(0)
     sh = prepare_flat(eng, pols, data["resources"], data["probes"])
@@ -43,6 +50,12 @@ for pols in (data["policies"], pols_b):
     torch.cuda.synchronize()
     tables.append(eng.wrap_table(d_in.data_ptr(), d_eg.data_ptr(), d_st.data_ptr()))
     planes.append((d_in, d_eg, d_st))
+    if not flipped:  # table A's copy with 64 directed egress bits flipped (source i * P // 64, destination 7919 i mod P)
+        c_in, c_eg = torch.clone(d_in), torch.clone(d_eg)
+        for i in range(64):
+            s_, d_ = i * P // 64, (7919 * i + 63) % P
+            c_eg[s_, i % K, d_ // 64] ^= (1 << (d_ % 64)) - (1 << 64 if d_ % 64 == 63 else 0)
+        flipped = [eng.wrap_table(c_in.data_ptr(), c_eg.data_ptr(), d_st.data_ptr()), c_in, c_eg]
     eng.close()  # (a table outlives its context; the front's scratch goes)
 ta, tb = tables
 plane_gb = P * K * W * 8 / 1e9
@@ -79,8 +92,16 @@ def fill_gbs():
     return 2 * scratch.numel() * 8 / (min(ms) * 1e-3) / 1e9
 
 
+tc = flipped[0]
+page = np.zeros(P * K, CELL_DTYPE)  # cap = P * K always makes progress
+LISTINGS = {
+    "find_count": lambda: (ta.compare_find(tb, ignore_loopback=True, cap=0), ta.find("combined", (CONN_BLOCKED,), cap=0)),
+    "compare_find": lambda: ta.compare_find(tc, ignore_loopback=True, out=page),
+    "find_dense": lambda: ta.find("combined", (CONN_ALLOWED,), out=page),
+}
+
 if mode == "run":
-    f = (lambda: ta.counts()) if pos[0] == "counts" else (lambda: ta.compare(tb, d_diff=diff.data_ptr()))
+    f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS}[pos[0]]
     for _ in range(n_run):
         f()
     sys.exit(0)
@@ -103,6 +124,36 @@ res["counts_gbs"] = 2 * plane_gb / res["counts_ms"] * 1e3
 res["compare_gbs"] = (4 * plane_gb + P * W * 8 / 1e9) / res["compare_ms"] * 1e3
 res["read2_gbs"] = 2 * plane_gb / res["read2_ms"] * 1e3
 res["read4_gbs"] = 4 * plane_gb / res["read4_ms"] * 1e3
+# the listings: pass 1 alone (the count-only calls) and whole pages, next to counts and compare above
+sparse, sparse_next, sparse_total = LISTINGS["compare_find"]()
+dense, dense_next, dense_total = LISTINGS["find_dense"]()
+res.update({
+    "compare_find_count_ms": timed(lambda: ta.compare_find(tb, ignore_loopback=True, cap=0), reps),
+    "find_count_ms": timed(lambda: ta.find("combined", (CONN_BLOCKED,), cap=0), reps),
+    "sparse_count_ms": timed(lambda: ta.compare_find(tc, ignore_loopback=True, cap=0), reps),
+    "sparse_page_ms": timed(LISTINGS["compare_find"], reps),
+    "sparse_records": len(sparse), "sparse_next": sparse_next, "sparse_total": sparse_total,
+    "dense_page_ms": timed(LISTINGS["find_dense"], reps),
+    "dense_count_ms": timed(lambda: ta.find("combined", (CONN_ALLOWED,), cap=0), reps),
+    "dense_records": len(dense), "dense_next": dense_next, "dense_total": dense_total,
+    "compare_find_total": ta.compare_find(tb, ignore_loopback=True, cap=0)[2],
+    "find_blocked_total": ta.find("combined", (CONN_BLOCKED,), cap=0)[2],
+})
+res["compare_find_count_over_compare"] = res["compare_find_count_ms"] / res["compare_nodiff_ms"]
+res["find_count_over_counts"] = res["find_count_ms"] / res["counts_ms"]
+res["sparse_pass2_ms"] = res["sparse_page_ms"] - res["sparse_count_ms"]
+res["dense_pass2_ms"] = res["dense_page_ms"] - res["dense_count_ms"]
+find_lines = [
+    f"find_count    compare_find count-only {res['compare_find_count_ms']:9.2f} ms  ({res['compare_find_count_over_compare']:.2f} x compare without d_diff, "
+    f"{4 * plane_gb / res['compare_find_count_ms'] * 1e3:.0f} GB/s of 4 planes; total {res['compare_find_total']})   "
+    f"find(Combined == blocked) count-only {res['find_count_ms']:9.2f} ms  ({res['find_count_over_counts']:.2f} x counts, "
+    f"{2 * plane_gb / res['find_count_ms'] * 1e3:.0f} GB/s of 2 planes; total {res['find_blocked_total']})",
+    f"compare_find  A against its copy with 64 egress bits flipped: page {res['sparse_page_ms']:9.2f} ms, pass 1 alone {res['sparse_count_ms']:9.2f} ms, "
+    f"so pass 2 and the copies {res['sparse_pass2_ms']:.2f} ms; {res['sparse_records']} records, s_next {res['sparse_next']}",
+    f"find_dense    one page of find(Combined == allowed), cap P*K = {P * K}: {res['dense_page_ms']:9.2f} ms, pass 1 alone {res['dense_count_ms']:9.2f} ms, "
+    f"so pass 2 and the copies {res['dense_pass2_ms']:.2f} ms; {res['dense_records']} records ({res['dense_records'] * 16 / 1e6:.1f} MB), "
+    f"s_next {res['dense_next']}, total {res['dense_total']}",
+]
 lines = [
     f"# {config}: P {P}, K {K}, W {W}; a plane is {plane_gb:.2f} GB; min of {reps} synchronous calls; the box's fill figure {res['fill_gbs']:.0f} GB/s",
     f"counts   {res['counts_ms']:9.2f} ms  {res['counts_gbs']:7.0f} GB/s of 2 planes   read of 2 planes {res['read2_ms']:9.2f} ms "
@@ -111,6 +162,7 @@ lines = [
     f"{res['read4_gbs']:7.0f} GB/s   ratio {res['compare_over_read']:.2f}   (without d_diff {res['compare_nodiff_ms']:.2f} ms)",
     f"Combined allowed {res['combined_allowed']}, blocked {res['combined_blocked']}, cells without a job {res['no_job']}; "
     f"pairs same / different / ignored {res['pairs_same_different_ignored']}",
+    *find_lines,
     json.dumps(res),
 ]
 print("\n".join(lines))
