@@ -57,6 +57,8 @@ EXPORTS = [
     "cyc_table_compare",
     "cyc_table_find",
     "cyc_table_compare_find",
+    "cyc_table_group_counts",
+    "cyc_table_group_compare",
     "cyc_table_shape",
     "cyc_table_error",
     "cyc_table_destroy",
@@ -194,6 +196,8 @@ def lib():
         pi64 = ctypes.POINTER(i64)
         L.cyc_table_find.argtypes = [vp, i, ctypes.c_uint32, i64, i64, i64, vp, i64, pi64, pi64, pi64]
         L.cyc_table_compare_find.argtypes = [vp, vp, i64, i64, i, i64, vp, i64, pi64, pi64, pi64]
+        L.cyc_table_group_counts.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp]
+        L.cyc_table_group_compare.argtypes = [vp, vp, vp, i64, i64, i64, i, vp, vp]
         L.cyc_table_shape.argtypes = [vp, ctypes.POINTER(i64), i]
         L.cyc_table_error.argtypes = [vp]
         L.cyc_table_error.restype = cp

@@ -98,6 +98,26 @@ class ComparisonTable:
             counts[p] = {c: int(n) for c, n in zip(COMPARISONS, v) if n}
         return counts
 
+    def _by_namespace(self, what: str, ignore_loopback: bool) -> dict:
+        """The cells sources' group_compare (cyc_table_group_compare on the device for DeviceTables) with the pods'
+        namespaces as groups: {(namespace from, namespace to): {comparison: count}}, zero counts left out."""
+        names, groups = self.kube._namespaces()
+        if not names:
+            return {}
+        k = self.kube.slots
+        c = self.kube.src.group_compare(self.simulated.src, groups, len(names), k.start, k.stop, bool(ignore_loopback))[what]
+        if what == "slots":
+            c = c.sum(axis=2)
+        return {(fr, to): {x: int(n) for x, n in zip(COMPARISONS, c[i, j]) if n} for i, fr in enumerate(names) for j, to in enumerate(names)}
+
+    def value_counts_by_namespace(self, ignore_loopback: bool = False) -> dict:
+        """value_counts (the (from, to) pairs) per pair of namespaces; an ignored loopback pair lies in (ns, ns)."""
+        return self._by_namespace("pairs", ignore_loopback)
+
+    def job_counts_by_namespace(self, ignore_loopback: bool = False) -> dict:
+        """The per-job counts of value_counts_by_protocol, summed over the jobs, per pair of namespaces."""
+        return self._by_namespace("slots", ignore_loopback)
+
     def different_jobs(self, ignore_loopback: bool, limit=None):
         """Yield (from, to, job key, kube Combined, simulated Combined) for every job counted as `different`
         (Item.ResultsByProtocol :14-20 under the loopback rule of :89-107), at most `limit` of them, in plane order

@@ -179,6 +179,205 @@ __global__ __launch_bounds__(1024) void k_table_tiles(TileArgs a) {
   }
 }
 
+// ---- The same pass split by pod group pair (cyc_table_group_counts, cyc_table_group_compare): which groups
+// (namespaces, say) reach which, and between which the two tables disagree.  The geometry is k_table_tiles';
+// what changes is where the popcounts go.  The host hands over, per 64-pod source word, the (group, 64-bit
+// mask) entries of the groups present in it, in pod order, so a group that runs over a word boundary is the
+// last entry of one word and the first of the next.  A block first copies the entries of its 16 source words
+// (1024 at most) to the LDS: read from global memory in the loop, every entry would be a dependent load that
+// the whole wave waits for.  Per tile step the wave walks the entries of its source word (the same for every
+// lane: LDS broadcast reads); the lane adds popc(word & mask) to a running sum per view, which it keeps while
+// consecutive entries carry the same source group.  On a change of source group the wave sums over its
+// runs of lanes with one destination group (a segmented scan: the three views' sums travel packed in one
+// 64-bit word) and the last lane of each run adds the sum into the block's LDS table, a packed 64-bit cell per
+// (source group, destination group) of the block; per slot the block adds the non-zero cells to the global
+// buffer.  The block-local dense numbers of the groups come from the host with the entries (it walks the pods
+// once anyway), so the kernel needs no numbering preamble.  A block with more than GT_CAP groups among its 1024
+// sources or its 1024 destinations adds the runs' sums straight to the global buffer instead.  Integer sums:
+// the result does not depend on the path or the order.
+constexpr uint32_t GT_CAP = 32;   // LDS table: GT_CAP source groups x GT_CAP destination groups of the block
+constexpr uint32_t GT_BITS = 21;  // a block tile holds at most 2^20 cells of a group pair per slot and view
+static_assert(GT_CAP * GT_CAP == 1024, "a thread of the block per LDS cell");
+
+struct GroupArgs {
+  TileArgs t;  // cnt: counts [nk][3][G][G] allowed cells of Ingress, Egress, Combined per (k, gs, gd), destination-
+               // group-minor; compare [nk + 1][G][G]: differing cells per (k, gs, gd) (loopback left out when it is
+               // ignored), then the differing pairs; then [G]: the differing pairs (d, d) per group
+  uint32_t G;
+  const uint32_t* ent_ptr;   // [WA + 1]: the entries of window word j are [ent_ptr[j], ent_ptr[j + 1])
+  const uint64_t* ent_mask;  // [E] the sources of the word that are in the group (and in the table's rows)
+  const uint32_t* ent_grp;   // [E] the group
+  const uint32_t* ent_loc;   // [E] its number among the groups of the block's 16 source words
+  const uint32_t* row_ptr;   // [grid.y + 1] -> row_grp: the groups of a block's sources by that number
+  const uint32_t* row_grp;
+  const int32_t* dst_grp;    // [P] group_of
+  const uint32_t* dst_loc;   // [P] the group's number among the groups of the block's 1024 destinations
+  const uint32_t* col_ptr;   // [grid.x + 1] -> col_grp
+  const uint32_t* col_grp;
+};
+
+template <bool CMP>
+__global__ __launch_bounds__(1024) void k_table_group_tiles(GroupArgs g) {
+  constexpr uint32_t V = CMP ? 1 : 3;
+  constexpr uint64_t FIELD = (1ull << GT_BITS) - 1;
+  __shared__ unsigned long long tab[GT_CAP * GT_CAP];
+  __shared__ uint64_t ent_mask[TT_WORDS * 64];  // the block's entries: mask, and group or its block-local number
+  __shared__ uint32_t ent_key[TT_WORDS * 64], ent_at[TT_WORDS + 1];
+  const TileArgs& a = g.t;
+  const uint32_t lane = threadIdx.x & 63, dw = blockIdx.x * TT_WORDS + (threadIdx.x >> 6);
+  // (a wave past the last destination word loads nothing and only keeps the block's barriers)
+  const uint32_t d = dw * 64 + lane;
+  const int32_t gd = dw < a.W && d < a.P ? g.dst_grp[d] : -1;
+  const bool d_ok = gd >= 0;  // (a pod without a group is no destination: its lane holds zeros throughout)
+  const uint32_t ld = d_ok ? g.dst_loc[d] : 0;
+  const uint32_t sw0 = a.w0 + blockIdx.y * TT_WORDS, sw_end = min(sw0 + TT_WORDS, a.w0 + a.WA);
+  const uint64_t eg_step = uint64_t(64) * a.K * a.W, GG = uint64_t(g.G) * g.G;
+  const uint32_t rs = g.row_ptr[blockIdx.y], cs = g.col_ptr[blockIdx.x];
+  const bool use_lds = g.row_ptr[blockIdx.y + 1] - rs <= GT_CAP && g.col_ptr[blockIdx.x + 1] - cs <= GT_CAP;
+  {
+    const uint32_t e0 = g.ent_ptr[sw0 - a.w0], n_ent = g.ent_ptr[sw_end - a.w0] - e0;
+    if (threadIdx.x <= sw_end - sw0) ent_at[threadIdx.x] = g.ent_ptr[sw0 - a.w0 + threadIdx.x] - e0;
+    if (threadIdx.x < n_ent) {
+      ent_mask[threadIdx.x] = g.ent_mask[e0 + threadIdx.x];
+      ent_key[threadIdx.x] = (use_lds ? g.ent_loc : g.ent_grp)[e0 + threadIdx.x];
+    }
+  }
+  // the wave's runs of lanes with one destination group: the first lane of the lane's run, and whether it is the last
+  // (the shuffle stands before the condition: behind `lane == 0 ||` lane 0 would sit it out and lane 1 read a zero)
+  const int32_t gd_before = __shfl_up(gd, 1, 64);
+  const uint64_t heads = __ballot(lane == 0 || gd != gd_before);
+  const uint32_t run_start = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
+  const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1);
+  tab[threadIdx.x] = 0;
+  __syncthreads();
+
+  uint32_t cur = ~0u, n[V];  // the source group of the running sums (its block-local number on the LDS path)
+#pragma unroll
+  for (uint32_t v = 0; v < V; v++) n[v] = 0;
+  // The running sums go to slot `slot` of the buffer.  Wave-uniform: every lane of the wave calls it together.
+  auto flush = [&](uint32_t slot) {
+    uint64_t s = n[0];
+    if (!CMP) s |= uint64_t(n[1]) << GT_BITS | uint64_t(n[2]) << (2 * GT_BITS);
+#pragma unroll
+    for (uint32_t v = 0; v < V; v++) n[v] = 0;
+    if (cur == ~0u || __ballot(s != 0) == 0) return;
+    // a lane's sum is at most 1024 per view and a run's at most 2^16: the fields do not carry into each other
+#pragma unroll
+    for (uint32_t i = 1; i < 64; i <<= 1) {
+      const uint32_t lo = __shfl_up(uint32_t(s), i, 64), hi = __shfl_up(uint32_t(s >> 32), i, 64);
+      if (lane >= run_start + i) s += uint64_t(hi) << 32 | lo;
+    }
+    if (!tail || !d_ok || !s) return;
+    if (use_lds) {
+      atomicAdd(&tab[cur * GT_CAP + ld], (unsigned long long)s);
+    } else {
+      unsigned long long* o = a.cnt + uint64_t(slot) * V * GG + uint64_t(cur) * g.G + uint32_t(gd);
+#pragma unroll
+      for (uint32_t v = 0; v < V; v++) {
+        const uint64_t c = (s >> (v * GT_BITS)) & FIELD;
+        if (c) atomicAdd(o + v * GG, (unsigned long long)c);
+      }
+    }
+  };
+  // the words of a tile step (bits over the sources of word sw), split by the source groups of the word
+  auto add_word = [&](uint32_t sw, uint64_t x0, uint64_t x1, uint64_t x2, uint32_t slot) {
+    const uint32_t e_end = __builtin_amdgcn_readfirstlane(ent_at[sw - sw0 + 1]);
+    for (uint32_t e = __builtin_amdgcn_readfirstlane(ent_at[sw - sw0]); e < e_end; e++) {
+      const uint32_t key = __builtin_amdgcn_readfirstlane(ent_key[e]);
+      if (key != cur) {
+        flush(slot);
+        cur = key;
+      }
+      const uint64_t m = ent_mask[e];
+      n[0] += __popcll(x0 & m);
+      if (!CMP) n[1] += __popcll(x1 & m), n[2] += __popcll(x2 & m);
+    }
+  };
+  // the end of a slot: the last running sums, then the block's LDS cells go to the global buffer
+  auto drain = [&](uint32_t slot) {
+    flush(slot);
+    cur = ~0u;
+    if (!use_lds) return;
+    __syncthreads();
+    const unsigned long long s = tab[threadIdx.x];
+    if (s) {
+      tab[threadIdx.x] = 0;
+      unsigned long long* o = a.cnt + uint64_t(slot) * V * GG + uint64_t(g.row_grp[rs + threadIdx.x / GT_CAP]) * g.G +
+                              g.col_grp[cs + threadIdx.x % GT_CAP];
+#pragma unroll
+      for (uint32_t v = 0; v < V; v++) {
+        const uint64_t c = (s >> (v * GT_BITS)) & FIELD;
+        if (c) atomicAdd(o + v * GG, (unsigned long long)c);
+      }
+    }
+    __syncthreads();
+  };
+
+  uint64_t diff[CMP ? TT_WORDS : 1];
+#pragma unroll
+  for (uint32_t j = 0; j < (CMP ? TT_WORDS : 1); j++) diff[j] = 0;
+  for (uint32_t kk = 0; kk < a.nk; kk++) {
+    const uint32_t k = a.k_lo + kk;
+    const uint8_t sa = d_ok ? a.a.status[uint64_t(d) * a.K + k] : uint8_t(CYC_JOB_NONE);
+    const uint8_t sb = CMP && d_ok ? a.b.status[uint64_t(d) * a.K + k] : uint8_t(CYC_JOB_NONE);
+    // counts: the lane's cells are VALID; compare: both are (k_table_tiles: otherwise the statuses decide)
+    const bool on = CMP ? sa == CYC_JOB_VALID && sb == CYC_JOB_VALID : sa == CYC_JOB_VALID;
+    const bool all_differ = CMP && !on && sa != sb;
+    const bool any_on = __ballot(on) != 0, any_word = any_on || __ballot(all_differ) != 0;
+    const uint64_t in_at = (uint64_t(d) * a.K + k) * a.WA + (sw0 - a.w0);
+    const uint64_t eg_at = (uint64_t(sw0 * 64 + lane - a.s_lo) * a.K + k) * a.W + dw;
+#pragma unroll 1
+    for (uint32_t h = 0; h < TT_WORDS; h += TT_BATCH) {
+      // the lane's ingress words of TT_BATCH tiles, loaded back to back (k_table_tiles)
+      uint64_t ia[TT_BATCH], ib[TT_BATCH];
+#pragma unroll
+      for (uint32_t j = 0; j < TT_BATCH; j++) {
+        const bool ld_on = on && sw0 + h + j < sw_end;
+        ia[j] = ld_on ? a.a.in[in_at + h + j] : 0ull;
+        ib[j] = CMP && ld_on ? a.b.in[in_at + h + j] : 0ull;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < TT_BATCH; j++) {
+        const uint32_t sw = sw0 + h + j;
+        if (sw >= sw_end) continue;
+        __syncthreads();  // the block's waves take a tile step together (its egress lines: header comment)
+        if (!any_word) continue;
+        const uint64_t m = source_mask(sw, a.s_hi);
+        uint64_t ta = 0, tb = 0;
+        if (any_on) {
+          const bool s_ok = dw < a.W && sw * 64 + lane < a.s_hi;
+          ta = transpose64(s_ok ? a.a.eg[eg_at + (h + j) * eg_step] : 0ull, lane);
+          if (CMP) tb = transpose64(s_ok ? a.b.eg[eg_at + (h + j) * eg_step] : 0ull, lane);
+        }
+        if (CMP) {
+          uint64_t x = (on ? (ta & ia[j]) ^ (tb & ib[j]) : all_differ ? ~0ull : 0ull) & m;
+          // (h is not unrolled: a select per batch keeps diff[] in registers)
+#pragma unroll
+          for (uint32_t hh = 0; hh < (CMP ? TT_WORDS : 1); hh += TT_BATCH) diff[hh + (CMP ? j : 0)] |= h == hh ? x : 0ull;
+          if (a.ignore_loopback && sw == dw) x &= ~(1ull << lane);
+          add_word(sw, sa != CYC_JOB_NONE ? x : 0ull, 0, 0, kk);  // (per job: only cells where a holds one)
+        } else {
+          const uint64_t i = on ? ia[j] & m : 0ull, e = on ? ta & m : 0ull;
+          add_word(sw, i, e, e & i, kk);
+        }
+      }
+    }
+    drain(kk);
+  }
+  if (CMP) {
+    // the pairs: the lane's OR over the slots, split by the same entries, as slot nk of the buffer
+#pragma unroll 1
+    for (uint32_t j = 0; sw0 + j < sw_end; j++) {
+      uint64_t x = 0;
+#pragma unroll
+      for (uint32_t jj = 0; jj < (CMP ? TT_WORDS : 1); jj++) x = j == jj ? diff[jj] : x;
+      add_word(sw0 + j, x, 0, 0, a.nk);
+      if (sw0 + j == dw && ((x >> lane) & 1)) atomicAdd(a.cnt + (uint64_t(a.nk) + 1) * GG + uint32_t(gd), 1ull);
+    }
+    drain(a.nk);
+  }
+}
+
 // ---- A partial target-row table: ingress rows of its destinations, egress rows of its sources.  No
 // cell has both, so there is no Combined and no transpose: two row reductions.
 struct RowCountArgs {

@@ -769,6 +769,243 @@ int cyc_table_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, 
   });
 }
 
+// ---------------------------------------------------------------- counts and comparison per pod-group pair
+constexpr int64_t GROUP_CELLS_MAX = int64_t(1) << 27;  // n_groups^2 * slots of one call
+
+// The checks the two group entry points share; nullptr when the arguments are fine.
+static const char* group_args_bad(const cyc_table* t, const int32_t* group_of, int64_t G, int64_t k_lo, int64_t k_hi, std::string& why) {
+  if (!group_of) return "null group_of";
+  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return "slot range out of bounds";
+  if (G < 1) return "n_groups must be at least 1";
+  if (G > GROUP_CELLS_MAX || G * G * std::max<int64_t>(k_hi - k_lo, 1) > GROUP_CELLS_MAX)
+    return "n_groups^2 * slots exceeds the limit of 134217728 (2^27)";
+  for (int64_t p = 0; p < int64_t(t->P); p++)
+    if (group_of[p] < -1 || group_of[p] >= G) {
+      why = "group_of[" + std::to_string(p) + "] = " + std::to_string(group_of[p]) + " is neither -1 nor a group in [0, " +
+            std::to_string(G) + ")";
+      return why.c_str();
+    }
+  return nullptr;
+}
+
+// What k_table_group_tiles takes of a grouping (GroupArgs, dev_table.hpp), from one walk over the pods: the
+// (group, mask) entries of every source word of the table in pod order, the groups of every block row of 16
+// source words and block column of 1024 destinations numbered in order of appearance, and the group sizes
+// for the host-side terms.
+extern "C++" {
+struct GroupTables {
+  std::vector<uint32_t> ent_ptr{0}, ent_grp, ent_loc, row_ptr, row_grp, dst_loc, col_ptr, col_grp;
+  std::vector<uint64_t> ent_mask;
+  std::vector<int64_t> n_src, n_dst;  // pods of a group among the table's sources, among all destinations
+  DevBuf dev[10];
+
+  GroupTables(const cyc_table* t, const int32_t* group_of, int64_t G) : n_src(size_t(G), 0), n_dst(size_t(G), 0) {
+    constexpr uint32_t NONE = ~0u;
+    const size_t n = size_t(G);
+    std::vector<uint32_t> word_of(n, NONE), ent_of(n), blk_of(n, NONE), loc_of(n);
+    for (uint32_t j = 0; j < t->wa; j++) {
+      if (j % TT_WORDS == 0) row_ptr.push_back(uint32_t(row_grp.size()));
+      for (uint32_t b = 0; b < 64; b++) {
+        const int64_t s = int64_t(t->w0 + j) * 64 + b;
+        if (s < t->row_lo || s >= t->row_hi || group_of[s] < 0) continue;
+        const uint32_t g = uint32_t(group_of[s]);
+        n_src[g]++;
+        if (word_of[g] != j) {
+          if (blk_of[g] != j / TT_WORDS) {
+            blk_of[g] = j / TT_WORDS, loc_of[g] = uint32_t(row_grp.size()) - row_ptr.back();
+            row_grp.push_back(g);
+          }
+          word_of[g] = j, ent_of[g] = uint32_t(ent_grp.size());
+          ent_grp.push_back(g), ent_loc.push_back(loc_of[g]), ent_mask.push_back(0);
+        }
+        ent_mask[ent_of[g]] |= 1ull << b;
+      }
+      ent_ptr.push_back(uint32_t(ent_grp.size()));
+    }
+    row_ptr.push_back(uint32_t(row_grp.size()));
+    std::fill(blk_of.begin(), blk_of.end(), NONE);
+    dst_loc.assign(t->P, 0);
+    for (uint32_t d = 0; d < t->P; d++) {
+      if (d % (TT_WORDS * 64) == 0) col_ptr.push_back(uint32_t(col_grp.size()));
+      if (group_of[d] < 0) continue;
+      const uint32_t g = uint32_t(group_of[d]);
+      n_dst[g]++;
+      if (blk_of[g] != d / (TT_WORDS * 64)) {
+        blk_of[g] = d / (TT_WORDS * 64), loc_of[g] = uint32_t(col_grp.size()) - col_ptr.back();
+        col_grp.push_back(g);
+      }
+      dst_loc[d] = loc_of[g];
+    }
+    col_ptr.push_back(uint32_t(col_grp.size()));
+  }
+
+  // (asynchronous: the vectors live until the caller has synchronised the stream)
+  template <class T>
+  const T* put(int i, const T* v, size_t n, hipStream_t st) {
+    dev[i].alloc(std::max<size_t>(n * sizeof(T), 16));
+    if (n) HIPCHK(hipMemcpyAsync(dev[i].p, v, n * sizeof(T), hipMemcpyHostToDevice, st));
+    return dev[i].as<T>();
+  }
+  GroupArgs args(const TileArgs& tile, const int32_t* group_of, int64_t G, hipStream_t st) {
+    GroupArgs g{};
+    g.t = tile, g.G = uint32_t(G);
+    g.ent_ptr = put(0, ent_ptr.data(), ent_ptr.size(), st);
+    g.ent_mask = put(1, ent_mask.data(), ent_mask.size(), st);
+    g.ent_grp = put(2, ent_grp.data(), ent_grp.size(), st);
+    g.ent_loc = put(3, ent_loc.data(), ent_loc.size(), st);
+    g.row_ptr = put(4, row_ptr.data(), row_ptr.size(), st);
+    g.row_grp = put(5, row_grp.data(), row_grp.size(), st);
+    g.dst_grp = put(6, group_of, tile.P, st);
+    g.dst_loc = put(7, dst_loc.data(), dst_loc.size(), st);
+    g.col_ptr = put(8, col_ptr.data(), col_ptr.size(), st);
+    g.col_grp = put(9, col_grp.data(), col_grp.size(), st);
+    return g;
+  }
+};
+}  // extern "C++"
+
+int cyc_table_group_counts(cyc_table* t, const int32_t* group_of, int64_t n_groups, int64_t k_lo, int64_t k_hi, int64_t* ingress,
+                           int64_t* egress, int64_t* combined, int64_t* no_job) {
+  if (!t) return CYC_ERR_ARG;
+  auto bad = [&](const std::string& m) {
+    t->err = m;
+    return (int)CYC_ERR_ARG;
+  };
+  std::string why;
+  if (const char* m = group_args_bad(t, group_of, n_groups, k_lo, k_hi, why)) return bad(m);
+  if (!ingress && !egress && !combined && !no_job) return bad("no output requested");
+  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
+  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, G = n_groups, GG = G * G, rows = t->row_hi - t->row_lo;
+  int64_t* out[3] = {ingress, egress, combined};
+  for (int x = 0; x < 3; x++)
+    if (out[x]) std::fill(out[x], out[x] + GG * nk * 6, int64_t(0));
+  if (no_job) std::fill(no_job, no_job + GG, int64_t(0));
+  if (!nk || !P) return (int)CYC_OK;
+  return table_guarded(t, [&]() -> int {
+    DeviceGuard dg(t->device);
+    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    // allowed cells [nk][3][G][G] of Ingress, Egress, Combined
+    const uint64_t n_cnt = uint64_t(nk) * 3 * GG;
+    std::vector<unsigned long long> cnt(n_cnt, 0);
+    std::vector<uint8_t> st(size_t(P) * K);
+    GroupTables gt(t, group_of, G);
+    DevBuf d_cnt;
+    if (rows) {
+      d_cnt.alloc(n_cnt * 8);
+      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
+      GroupArgs a = gt.args(tile_args(t, k_lo, k_hi), group_of, G, t->stream);
+      a.t.cnt = d_cnt.as<unsigned long long>();
+      k_table_group_tiles<false><<<tile_grid(t), 1024, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
+    }
+    HIPCHK(hipMemcpyAsync(st.data(), t->status, st.size(), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    // the status-only terms, as cyc_table_counts': per (destination group, slot) the destinations of each
+    // status, times the sources of the source group
+    std::vector<int64_t> by_status(size_t(G) * nk * 4, 0);  // [gd][kk][cyc_job_status]
+    for (int64_t d = 0; d < P; d++)
+      if (group_of[d] >= 0)
+        for (int64_t kk = 0; kk < nk; kk++) by_status[size_t((group_of[d] * nk + kk) * 4 + (st[size_t(d * K + k_lo + kk)] & 3))]++;
+    for (int64_t gs = 0; gs < G; gs++) {
+      const int64_t ns = gt.n_src[size_t(gs)];
+      if (!ns) continue;
+      for (int64_t gd = 0; gd < G; gd++) {
+        if (!gt.n_dst[size_t(gd)]) continue;
+        for (int64_t kk = 0; kk < nk; kk++) {
+          const int64_t* s = &by_status[size_t((gd * nk + kk) * 4)];
+          const int64_t valid = ns * s[CYC_JOB_VALID], bpp = ns * s[CYC_JOB_BAD_PORT_PROTOCOL], bnp = ns * s[CYC_JOB_BAD_NAMED_PORT];
+          const size_t at = size_t(((gs * G + gd) * nk + kk) * 6);
+          for (int x = 0; x < 3; x++) {
+            if (!out[x]) continue;
+            const int64_t allowed = int64_t(cnt[size_t((kk * 3 + x) * GG + gs * G + gd)]);
+            int64_t* o = out[x] + at;
+            o[CYC_CONN_ALLOWED] = allowed, o[CYC_CONN_BLOCKED] = valid - allowed;
+            if (x == 1) o[CYC_CONN_UNKNOWN] = bpp + bnp;
+            else o[CYC_CONN_INVALID_PORT_PROTOCOL] = bpp, o[CYC_CONN_INVALID_NAMED_PORT] = bnp;
+          }
+          if (no_job) no_job[gs * G + gd] += ns * s[CYC_JOB_NONE];
+        }
+      }
+    }
+    return (int)CYC_OK;
+  });
+}
+
+int cyc_table_group_compare(cyc_table* ta, cyc_table* tb, const int32_t* group_of, int64_t n_groups, int64_t k_lo, int64_t k_hi,
+                            int ignore_loopback, int64_t* pair_counts, int64_t* slot_counts) {
+  if (!ta) return CYC_ERR_ARG;
+  cyc_table* t = ta;
+  auto bad = [&](const std::string& m) {
+    t->err = m;
+    return (int)CYC_ERR_ARG;
+  };
+  if (!tb) return bad("null table");
+  if (!pair_counts) return bad("no output requested");
+  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition ||
+      ta->row_lo != tb->row_lo || ta->row_hi != tb->row_hi)
+    return bad("cannot compare tables of different devices, shapes, partitions or rows");
+  std::string why;
+  if (const char* m = group_args_bad(t, group_of, n_groups, k_lo, k_hi, why)) return bad(m);
+  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
+  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, G = n_groups, GG = G * G, rows = t->row_hi - t->row_lo;
+  std::fill(pair_counts, pair_counts + GG * 3, int64_t(0));
+  if (slot_counts) std::fill(slot_counts, slot_counts + GG * nk * 3, int64_t(0));
+  if (!P) return (int)CYC_OK;
+  return table_guarded(t, [&]() -> int {
+    DeviceGuard dg(t->device);
+    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    // [nk + 1][G][G]: differing cells per slot, then the differing pairs; then [G]: differing pairs (d, d)
+    const uint64_t n_cnt = uint64_t(nk + 1) * GG + G;
+    std::vector<unsigned long long> cnt(n_cnt, 0);
+    std::vector<uint8_t> sa(size_t(P) * K);
+    GroupTables gt(t, group_of, G);
+    if (rows) {
+      DevBuf d_cnt;
+      d_cnt.alloc(n_cnt * 8);
+      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
+      GroupArgs a = gt.args(tile_args(t, k_lo, k_hi), group_of, G, t->stream);
+      a.t.b = TablePlanes{tb->in, tb->eg, tb->status};
+      a.t.ignore_loopback = ignore_loopback ? 1u : 0u;
+      a.t.cnt = d_cnt.as<unsigned long long>();
+      k_table_group_tiles<true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipMemcpyAsync(sa.data(), ta->status, sa.size(), hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipStreamSynchronize(t->stream));  // (d_cnt is freed after it)
+    }
+    // the terms of cyc_table_compare, per group pair: jobs[gd][kk] = destinations of the group where a holds a
+    // job, loop[g][kk] = those among the table's sources (the loopback cells)
+    std::vector<int64_t> jobs(size_t(G) * nk, 0), loop(size_t(G) * nk, 0);
+    if (rows)
+      for (int64_t d = 0; d < P; d++)
+        if (group_of[d] >= 0)
+          for (int64_t kk = 0; kk < nk; kk++)
+            if (sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE) {
+              jobs[size_t(group_of[d] * nk + kk)]++;
+              if (ignore_loopback && d >= t->row_lo && d < t->row_hi) loop[size_t(group_of[d] * nk + kk)]++;
+            }
+    for (int64_t gs = 0; gs < G; gs++) {
+      const int64_t ns = gt.n_src[size_t(gs)];
+      if (!ns) continue;
+      for (int64_t gd = 0; gd < G; gd++) {
+        const int64_t self = gs == gd ? 1 : 0;
+        int64_t* p = pair_counts + (gs * G + gd) * 3;
+        p[2] = ignore_loopback ? self * ns : 0;
+        p[1] = int64_t(cnt[size_t(nk * GG + gs * G + gd)]) - (ignore_loopback ? self * int64_t(cnt[size_t((nk + 1) * GG + gs)]) : 0);
+        p[0] = ns * gt.n_dst[size_t(gd)] - p[1] - p[2];
+        for (int64_t kk = 0; slot_counts && kk < nk; kk++) {
+          int64_t* v = slot_counts + ((gs * G + gd) * nk + kk) * 3;
+          v[2] = self * loop[size_t(gs * nk + kk)];
+          v[1] = int64_t(cnt[size_t(kk * GG + gs * G + gd)]);
+          v[0] = ns * jobs[size_t(gd * nk + kk)] - v[1] - v[2];
+        }
+      }
+    }
+    return (int)CYC_OK;
+  });
+}
+
 // ---------------------------------------------------------------- which cells: find and compare_find
 static_assert(sizeof(cyc_cell) == 16, "cyc_cell is one 16-byte store");
 constexpr uint32_t FIND_LDS_SLOTS = 32;      // 2 KB of words per slot and wave: up to here they fit 64 KB of LDS

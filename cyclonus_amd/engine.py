@@ -376,6 +376,43 @@ class DeviceTable:
             out["diff"] = diff
         return out
 
+    def _groups(self, groups, n_groups):
+        g = np.ascontiguousarray(groups, np.int32)
+        if g.shape != (self.pods,):
+            raise ValueError(f"groups must hold one group id per pod ({self.pods}), got shape {g.shape}")
+        return g, int(g.max(initial=-1)) + 1 if n_groups is None else int(n_groups)
+
+    GROUP_CELLS_MAX = 1 << 27  # n_groups^2 * slots of one call (include/cyclonus_hip.h)
+
+    def _group_shape(self, G, k_lo, k_hi):
+        """(G, G, k) of the outputs; empty where the library refuses the arguments (it writes nothing then)."""
+        nk = k_hi - k_lo
+        ok = 0 <= k_lo <= k_hi <= self.slots and G >= 1 and G * G * max(nk, 1) <= self.GROUP_CELLS_MAX
+        return (G, G, nk) if ok else (0, 0, 0)
+
+    def group_counts(self, groups, n_groups=None, k_lo=0, k_hi=None, want=("ingress", "egress", "combined", "no_job")):
+        """cyc_table_group_counts: counts split by pod group pair.  groups: an int32 group id per pod (-1: the pod
+        is left out); n_groups defaults to max(groups) + 1.  {name: i64 [G, G, k, 6]} cells per (source group,
+        destination group, slot, cyc_connectivity code), and "no_job": i64 [G, G]."""
+        k_hi = self.slots if k_hi is None else k_hi
+        g, G = self._groups(groups, n_groups)
+        shape = self._group_shape(G, k_lo, k_hi)
+        out = {n: np.zeros(shape[:2] if n == "no_job" else shape + (6,), np.int64) for n in want}
+        ptr = [out[n].ctypes.data if n in out else None for n in ("ingress", "egress", "combined", "no_job")]
+        self._check(lib().cyc_table_group_counts(self._t, g.ctypes.data, G, int(k_lo), int(k_hi), *ptr))
+        return out
+
+    def group_compare(self, other: "DeviceTable", groups, n_groups=None, k_lo=0, k_hi=None, ignore_loopback=False):
+        """cyc_table_group_compare(self, other): compare split by pod group pair: {"pairs": i64 [G, G, 3],
+        "slots": i64 [G, G, k, 3]} in (same, different, ignored) order."""
+        k_hi = self.slots if k_hi is None else k_hi
+        g, G = self._groups(groups, n_groups)
+        shape = self._group_shape(G, k_lo, k_hi)
+        out = {"pairs": np.zeros(shape[:2] + (3,), np.int64), "slots": np.zeros(shape + (3,), np.int64)}
+        self._check(lib().cyc_table_group_compare(self._t, other._t, g.ctypes.data, G, int(k_lo), int(k_hi), int(bool(ignore_loopback)),
+                                                  out["pairs"].ctypes.data, out["slots"].ctypes.data))
+        return out
+
     def _find(self, call, k_lo, k_hi, s_from, cap, out):
         """One page of a listing: (records, s_next, total).  cap None: pods * slots of the range, which always
         makes progress; cap 0 without `out`: the count-only call.  `out`: a CELL_DTYPE array to write into (cap

@@ -209,6 +209,74 @@ class PlaneCells:
             out["diff"] = diff
         return out
 
+    # The same two split by pod group pair (cyc_table_group_counts / cyc_table_group_compare), cell by cell:
+    # what DeviceTable.group_counts / group_compare are tested against.
+    def _groups(self, groups, n_groups):
+        P = self.status.shape[0]
+        g = np.asarray(groups, np.int64)
+        if g.shape != (P,):
+            raise ValueError(f"groups must hold one group id per pod ({P}), got shape {g.shape}")
+        G = int(g.max(initial=-1)) + 1 if n_groups is None else int(n_groups)
+        if G < 1:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "n_groups must be at least 1")
+        bad = np.nonzero((g < -1) | (g >= G))[0]
+        if len(bad):
+            raise _lib.CyclonusError(_lib.ERR_ARG, f"group_of[{bad[0]}] = {g[bad[0]]} is neither -1 nor a group in [0, {G})")
+        return g, G
+
+    def _group_index(self, g, lo, hi, nk):
+        """For the cells [lo:hi, P, nk] of a source chunk: which have both pods in a group, and their (source
+        group, destination group, slot) indices, each broadcast to the chunk's shape."""
+        shape = (hi - lo, len(g), nk)
+        gs, gd, kk = g[lo:hi, None, None], g[None, :, None], np.arange(nk)[None, None, :]
+        return (np.broadcast_to((gs >= 0) & (gd >= 0), shape), np.broadcast_to(gs, shape), np.broadcast_to(gd, shape),
+                np.broadcast_to(kk, shape))
+
+    def group_counts(self, groups, n_groups=None, k_lo=0, k_hi=None, want=("ingress", "egress", "combined", "no_job")):
+        """cyc_table_group_counts: {name: i64 [G, G, k, 6]} cells per (source group, destination group, slot,
+        Connectivity code), "no_job": i64 [G, G].  groups: a group id per pod, -1 = the pod is left out."""
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        g, G = self._groups(groups, n_groups)
+        P, chunks = self._source_chunks()
+        nk = max(k_hi - k_lo, 0)
+        out = {n: np.zeros((G, G, nk, 6), np.int64) for n in ("ingress", "egress", "combined")}
+        out["no_job"] = np.zeros((G, G), np.int64)
+        for lo, hi in chunks:
+            cells = self.cells(lo, hi, 0, P, k_lo, k_hi)
+            keep, gs, gd, kk = self._group_index(g, lo, hi, nk)
+            for n, codes in cells.items():
+                job = keep & (codes != _lib.CONN_NO_JOB)
+                np.add.at(out[n], (gs[job], gd[job], kk[job], codes[job]), 1)
+            none = keep & (cells["combined"] == _lib.CONN_NO_JOB)
+            np.add.at(out["no_job"], (gs[none], gd[none]), 1)
+        return {n: out[n] for n in want}
+
+    def group_compare(self, other, groups, n_groups=None, k_lo=0, k_hi=None, ignore_loopback=False):
+        """cyc_table_group_compare(self, other): {"pairs": i64 [G, G, 3], "slots": i64 [G, G, k, 3]} in (same,
+        different, ignored) order: compare's pairs and per-job counts by (source group, destination group)."""
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        if other.status.shape != self.status.shape:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "cannot compare tables of different devices, shapes, partitions or rows")
+        g, G = self._groups(groups, n_groups)
+        P, chunks = self._source_chunks()
+        nk = max(k_hi - k_lo, 0)
+        pairs, slots = np.zeros((G, G, 3), np.int64), np.zeros((G, G, nk, 3), np.int64)
+        for lo, hi in chunks:
+            ca = self.cells(lo, hi, 0, P, k_lo, k_hi, want=("combined",))["combined"]
+            cb = other.cells(lo, hi, 0, P, k_lo, k_hi, want=("combined",))["combined"]
+            keep, gs, gd, kk = self._group_index(g, lo, hi, nk)
+            loopback = (np.arange(lo, hi)[:, None] == np.arange(P)[None, :]) & bool(ignore_loopback)
+            job = keep & (ca != _lib.CONN_NO_JOB)  # every job of the kube Item, once
+            ignored = job & loopback[:, :, None]
+            for x, m in enumerate((job & ~ignored & (ca == cb), job & ~ignored & (ca != cb), ignored)):
+                np.add.at(slots, (gs[m], gd[m], kk[m], x), 1)
+            item_differs = (ca != cb).any(axis=2)  # equalsDict over the job keys, NO_JOB included
+            keep, gs, gd, _ = (a[:, :, 0] for a in self._group_index(g, lo, hi, 1))
+            for x, m in enumerate((~loopback & ~item_differs, ~loopback & item_differs, loopback)):
+                m = m & keep
+                np.add.at(pairs, (gs[m], gd[m], x), 1)
+        return {"pairs": pairs, "slots": slots}
+
     # The listings (cyc_table_find / cyc_table_compare_find), cell by cell: the same contract as
     # DeviceTable.find / compare_find, which are tested against this restatement.
     def _page(self, matcher, k_lo, k_hi, s_from, cap):
@@ -368,6 +436,34 @@ class Table:
                 key = self._job_key(d, j)
                 yield (pods[int(r["s"])].pod_string(), pods[d].pod_string(),
                        JobResult(key, _CONN[int(r["ingress"])], _CONN[int(r["egress"])], _CONN[int(r["combined"])]))
+
+    # The level between the whole-table totals and the listings: per pair of namespaces (the reference prints
+    # whole pod tables only).
+    def _namespaces(self):
+        """(the pods' namespaces in sorted order, the int32 group id of every pod in plane order)."""
+        names = sorted({p.namespace for p in self.resources.pods})
+        at = {n: i for i, n in enumerate(names)}
+        return names, np.array([at[p.namespace] for p in self.resources.pods], np.int32)
+
+    def namespace_counts(self, view: str = "combined") -> dict:
+        """{(namespace from, namespace to): {Connectivity: jobs}} over the table's slots for the jobs' Ingress, Egress
+        or Combined (`view`), zero counts left out; counted by the cells source (cyc_table_group_counts on the device
+        for a DeviceTable)."""
+        if view not in _lib.VIEWS:
+            raise ValueError(f"invalid view: {view}")
+        names, groups = self._namespaces()
+        if not names:
+            return {}
+        c = self.src.group_counts(groups, len(names), self.slots.start, self.slots.stop, want=(view,))[view].sum(axis=2)
+        return {(fr, to): {_CONN[x]: int(c[i, j, x]) for x in range(6) if c[i, j, x]}
+                for i, fr in enumerate(names) for j, to in enumerate(names)}
+
+    def render_namespace_table(self, view: str = "combined") -> str:
+        """Namespaces by namespaces, each cell "<allowed jobs>/<jobs>"."""
+        names, _ = self._namespaces()
+        counts = self.namespace_counts(view)
+        rows = [[fr] + [f"{counts[fr, to].get(ALLOWED, 0)}/{sum(counts[fr, to].values())}" for to in names] for fr in names]
+        return render([""] + names, rows, row_line=False)
 
     # table.go:58-156
     def render_ingress(self) -> str:

@@ -370,6 +370,35 @@ int cyc_table_find(cyc_table* t, int view, uint32_t code_mask, int64_t k_lo, int
  * loopback.  a and b must match as in cyc_table_compare. */
 int cyc_table_compare_find(cyc_table* a, cyc_table* b, int64_t k_lo, int64_t k_hi, int ignore_loopback,
                            int64_t s_from, cyc_cell* cells, int64_t cap, int64_t* n, int64_t* s_next, int64_t* total);
+/* ---- The middle level between the totals and the listings: counts and comparison per pair of pod groups
+ * (which namespaces reach which; between which the two tables disagree).  The reference has no such summary:
+ * it prints whole pod tables (table.go:58-156, comparisontable.go:125-134).  The grouping is the caller's:
+ * group_of is a host int32[P], copied during the call; group_of[p] in [0, n_groups) or -1 = pod p is left out
+ * as source and as destination.  Any other value: CYC_ERR_ARG naming the first bad index.  n_groups >= 1 and
+ * n_groups^2 * max(k_hi - k_lo, 1) <= 2^27 (else CYC_ERR_ARG naming the limit).  Accepted tables as for
+ * cyc_table_find (a whole target-row table or a CYC_ROWS_SOURCE table; the shards of a partition add up to the
+ * whole table's result; a partial target-row table is refused); stream, lifetime, failures, plane bits at or
+ * beyond P and plane alignment as for cyc_table_counts: one pass over the planes, G = n_groups and
+ * nk = k_hi - k_lo below.  NULL group_of, a bad slot range or no output: CYC_ERR_ARG.  Exactly the stated
+ * number of elements of each output array is written; an empty slot range or P = 0 writes zeros (group_counts)
+ * and returns CYC_OK.
+ *
+ * ingress / egress / combined (host, each optional; at least one output, no_job included):
+ *   [((gs * G + gd) * nk + (k - k_lo)) * 6 + c] = number of cells (s, d, k) with group_of[s] == gs,
+ *   group_of[d] == gd and cyc_connectivity code c in that view: the codes of cyc_table_cells and
+ *   cyc_table_counts (a status-only code counts once for every source of the destination).
+ * no_job (optional): [gs * G + gd] = the cells with CYC_CONN_NO_JOB.
+ * When no pod is -1 the sums over (gs, gd) are cyc_table_counts' results. */
+int cyc_table_group_counts(cyc_table* t, const int32_t* group_of, int64_t n_groups, int64_t k_lo, int64_t k_hi,
+                           int64_t* ingress, int64_t* egress, int64_t* combined, int64_t* no_job);
+/* cyc_table_compare split by group pair (a and b must match as there):
+ *   pair_counts  [(gs * G + gd) * 3 + {same, different, ignored}]: (from, to) pairs; a pair is ignored iff
+ *                ignore_loopback and from == to, so ignored pairs land in (g, g).  Required.
+ *   slot_counts  optional [((gs * G + gd) * nk + k - k_lo) * 3 + ...]: per job as cyc_table_compare's slot_counts
+ *                (only cells where a holds a job, loopback tested before success, a job b lacks is different).
+ * When no pod is -1 the sums over (gs, gd) are cyc_table_compare's pair_counts and slot_counts. */
+int cyc_table_group_compare(cyc_table* a, cyc_table* b, const int32_t* group_of, int64_t n_groups, int64_t k_lo,
+                            int64_t k_hi, int ignore_loopback, int64_t* pair_counts, int64_t* slot_counts);
 /* out[0..7] = pods, slots, words, row_lo, row_hi, partition, ingress window first word, window words */
 int cyc_table_shape(const cyc_table* t, int64_t* out, int n);
 const char* cyc_table_error(const cyc_table* t);

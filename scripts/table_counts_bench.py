@@ -1,8 +1,9 @@
 """Config #3's whole table through cyc_table_counts and cyc_table_compare, against a plain read of the same planes.
 
     python scripts/table_counts_bench.py time [reps=3] [out=FILE]   # the table below, as text and one JSON line
-    python scripts/table_counts_bench.py run counts|compare|find_count|compare_find|find_dense [n=2]
-                                                                    # n calls of one pass (for a rocprofv3 --pmc run)
+    python scripts/table_counts_bench.py run counts|compare|find_count|compare_find|find_dense|group_counts|group_compare [n=2]
+                                                                    # n calls of one pass (for a rocprofv3 run)
+    python scripts/table_counts_bench.py group [reps=3] [out=FILE]  # the group leg alone (below)
 
 In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
 drawn with another seed; then, min over reps of the synchronous calls,
@@ -15,6 +16,11 @@ listings (cyc_table_find, cyc_table_compare_find) against counts and compare as 
   find_count    the count-only calls (pass 1 alone): compare_find of the two tables, find of Combined == blocked
   compare_find  the sparse case: table A against a torch.clone of its planes with 64 egress bits flipped, in one page
   find_dense    the dense case: one page of find(Combined == allowed) with cap = P * K
+The group leg (mode `group`): the pods' namespaces as groups (1000 for config #3), every slot, interleaved with their
+ungrouped counterparts on the same tables, min over reps of each:
+  group_counts   cyc_table_group_counts, all three views and no_job, against cyc_table_counts; and Combined alone
+  group_compare  cyc_table_group_compare with slot_counts against cyc_table_compare without d_diff
+and once, as checks, that the group results summed over the group pairs are the ungrouped results.
 """
 import json
 import os
@@ -92,6 +98,12 @@ def fill_gbs():
     return 2 * scratch.numel() * 8 / (min(ms) * 1e-3) / 1e9
 
 
+names = sorted({p["Namespace"] for p in data["resources"]["Pods"]})
+ns_at = {n: i for i, n in enumerate(names)}
+groups = np.array([ns_at[p["Namespace"]] for p in data["resources"]["Pods"]], np.int32)
+G = len(names)
+GROUP = {"group_counts": lambda: ta.group_counts(groups, G), "group_compare": lambda: ta.group_compare(tb, groups, G, ignore_loopback=True)}
+
 tc = flipped[0]
 page = np.zeros(P * K, CELL_DTYPE)  # cap = P * K always makes progress
 LISTINGS = {
@@ -101,9 +113,46 @@ LISTINGS = {
 }
 
 if mode == "run":
-    f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS}[pos[0]]
+    f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS, **GROUP}[pos[0]]
     for _ in range(n_run):
         f()
+    sys.exit(0)
+
+if mode == "group":
+    legs = {"counts": lambda: ta.counts(), "group_counts": GROUP["group_counts"],
+            "group_counts_combined": lambda: ta.group_counts(groups, G, want=("combined",)),
+            "compare_nodiff": lambda: ta.compare(tb, ignore_loopback=True), "group_compare": GROUP["group_compare"]}
+    gc, gp = GROUP["group_counts"](), GROUP["group_compare"]()  # (warm-up, and the checks)
+    c, r = ta.counts(), ta.compare(tb, ignore_loopback=True)
+    sums_ok = (all(np.array_equal(gc[n].sum(axis=(0, 1)), c[n]) for n in ("ingress", "egress", "combined")) and int(gc["no_job"].sum()) == c["no_job"]
+               and np.array_equal(gp["pairs"].sum(axis=(0, 1)), r["pairs"]) and np.array_equal(gp["slots"].sum(axis=(0, 1)), r["slots"]))
+    ms = {n: float("inf") for n in legs}
+    for _ in range(reps):  # interleaved: every leg once per round
+        for n, f in legs.items():
+            ms[n] = min(ms[n], timed(f, 1))
+    res = {"config": config, "pods": P, "slots": K, "words": W, "groups": G, "plane_gb": round(plane_gb, 3), "reps": reps,
+           **{n + "_ms": v for n, v in ms.items()}, "sums_equal_ungrouped": bool(sums_ok),
+           "group_counts_over_counts": ms["group_counts"] / ms["counts"],
+           "group_counts_combined_over_counts": ms["group_counts_combined"] / ms["counts"],
+           "group_compare_over_compare": ms["group_compare"] / ms["compare_nodiff"],
+           "group_counts_out_mb": sum(a.nbytes for a in gc.values()) / 1e6, "group_compare_out_mb": sum(a.nbytes for a in gp.values()) / 1e6,
+           "group_pairs_with_allowed": int((gc["combined"][..., CONN_ALLOWED].sum(axis=2) > 0).sum()),
+           "group_pairs_that_differ": int((gp["pairs"][..., 1] > 0).sum())}
+    lines = [
+        f"# {config}: P {P}, K {K}, W {W}, groups = the {G} namespaces; a plane is {plane_gb:.2f} GB; min of {reps} interleaved synchronous calls",
+        f"counts         {ms['counts']:9.2f} ms   group_counts  {ms['group_counts']:9.2f} ms  ratio {res['group_counts_over_counts']:.2f}  "
+        f"(host outputs {res['group_counts_out_mb']:.0f} MB; Combined alone {ms['group_counts_combined']:.2f} ms, ratio {res['group_counts_combined_over_counts']:.2f})",
+        f"compare        {ms['compare_nodiff']:9.2f} ms   group_compare {ms['group_compare']:9.2f} ms  ratio {res['group_compare_over_compare']:.2f}  "
+        f"(compare without d_diff; host outputs {res['group_compare_out_mb']:.0f} MB)",
+        f"group results summed over the group pairs equal the ungrouped results: {sums_ok}; namespace pairs with an allowed Combined cell "
+        f"{res['group_pairs_with_allowed']} of {G * G}, that differ between the tables {res['group_pairs_that_differ']}",
+        json.dumps(res),
+    ]
+    print("\n".join(lines))
+    if "out" in kw:
+        os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
+        with open(kw["out"], "w") as f:
+            f.write("\n".join(lines) + "\n")
     sys.exit(0)
 
 c = ta.counts()
