@@ -41,6 +41,7 @@ EXPORTS = [
     "cyc_probe_prepare",
     "cyc_probe_run",
     "cyc_probe_run_host",
+    "cyc_probe_target_effects",
     "cyc_last_timings",
     "cyc_last_classes",
     "cyc_last_emit",
@@ -92,6 +93,13 @@ PORT_ANY, PORT_NUMBER, PORT_NAME = 0, 1, 2
 # cyc_rows (row partitions for one-process-per-GPU runs)
 ROWS_TARGET, ROWS_SOURCE = 0, 1
 PARTITIONS = {"target": ROWS_TARGET, "source": ROWS_SOURCE}
+
+
+# cyc_direction and the effect kinds of cyc_probe_target_effects
+DIR_INGRESS, DIR_EGRESS = 0, 1
+DIRECTIONS = {"ingress": DIR_INGRESS, "egress": DIR_EGRESS}
+EFFECT_ALLOWING, EFFECT_DENYING, EFFECT_SOLE_ALLOWING, EFFECT_SOLE_DENYING = range(4)
+EFFECTS = ("allowing", "denying", "sole_allowing", "sole_denying")
 
 
 # cyc_view (cyc_table_find)
@@ -179,6 +187,7 @@ def lib():
         L.cyc_probe_prepare.argtypes = [vp, cp, sz, ctypes.POINTER(ProbeShape)]
         L.cyc_probe_run.argtypes = [vp, vp, vp, vp, vp, i64, i64]
         L.cyc_probe_run_host.argtypes = [vp, vp, vp, vp, i64, i64]
+        L.cyc_probe_target_effects.argtypes = [vp, i, i64, i64, i64, i64, vp, vp]
         L.cyc_last_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double), i]
         L.cyc_last_classes.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), i]
         L.cyc_last_emit.argtypes = [vp, cp, sz, ctypes.POINTER(i64)]

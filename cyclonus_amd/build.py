@@ -26,7 +26,7 @@ SOURCES_CPP = ["host.cpp"]
 SOURCES_HIP = ["engine.hip"]
 # engine.hip's stage headers (one translation unit) and the host headers
 HEADERS = ["cjson.hpp", "host.hpp", "tables.h", "route.hpp", "dev_select.hpp", "dev_peer_rows.hpp", "dev_slots.hpp", "dev_member.hpp",
-           "dev_class_rows.hpp", "dev_front.hpp", "dev_emit.hpp", "dev_query.hpp", "dev_gather.hpp", "dev_table.hpp", "ctx.hpp", "plan.hpp",
+           "dev_class_rows.hpp", "dev_front.hpp", "dev_emit.hpp", "dev_query.hpp", "dev_gather.hpp", "dev_table.hpp", "dev_effects.hpp", "ctx.hpp", "plan.hpp",
            "enqueue.hpp", "comm.hpp"]
 LIBS = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]  # RCCL: the table assembly's all-gathers (comm.hpp)
 

@@ -259,6 +259,12 @@ struct cyc_ctx {
   // by a prepare, by ensure_range and by cyc_set_option — a run only reads them.
   Route route = resolve_route(RouteIn{});
   RunState run;
+  // cyc_probe_target_effects' last call (cyc_get_option "effects_*"): how it was batched and the scratch it
+  // took.  Nothing of a run reads it.
+  struct EffectsLast {
+    int64_t batches = 0, launches = 0;  // class batches; (batch, word window) row builds
+    uint64_t scratch = 0;               // device bytes held at the peak
+  } effects;
   // multi-GPU table assembly (comm.hpp): the context's RCCL communicator, a second stream on which
   // gathered chunks are relaid out under the next chunk's all-gather, and the chunks' double buffer
   struct Comm {

@@ -149,6 +149,25 @@ class Engine:
             ),
         )
 
+    def target_effects(self, direction, row_lo: int = 0, row_hi: Optional[int] = None, k_lo: int = 0, k_hi: Optional[int] = None):
+        """cyc_probe_target_effects: which target decides.  direction: "ingress" / "egress" (or a cyc_direction);
+        rows [row_lo, row_hi) are the pods the direction's policies target.  -> (effects int64 [T, nk, 4], applies
+        int64 [T]): per target in primary-key order and slot the cells where it is in AllowingTargets, in
+        DenyingTargets, the only allowing target beside a denying one, the only applying target and denying
+        (_lib.EFFECTS); and the pods of the rows it applies to.  Needs a prepare, no run."""
+        d = _lib.DIRECTIONS.get(direction, direction)
+        sh = self.shape or {"pods": 0, "slots": 0, "targets_in": 0, "targets_eg": 0}
+        hi = sh["pods"] if row_hi is None else row_hi
+        k_hi = sh["slots"] if k_hi is None else k_hi
+        T = sh["targets_eg" if d == _lib.DIR_EGRESS else "targets_in"]
+        nk = max(int(k_hi) - int(k_lo), 0)
+        eff = np.zeros((T, nk, 4), np.int64)
+        app = np.zeros(T, np.int64)
+        # (empty numpy arrays still have a data pointer: an empty output is never the NULL the library refuses)
+        check(self._ctx, lib().cyc_probe_target_effects(self._ctx, int(d), int(row_lo), int(hi), int(k_lo), int(k_hi),
+                                                        ctypes.c_void_p(eff.ctypes.data), ctypes.c_void_p(app.ctypes.data)))
+        return eff, app
+
     def table(self, row_lo: int = 0, row_hi: Optional[int] = None, partition: str = "target") -> "DeviceTable":
         """Run the probe into a device-resident table (cyc_table_run_rows) for rows [row_lo, row_hi)."""
         hi = self.shape["pods"] if row_hi is None else row_hi

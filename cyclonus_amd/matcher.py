@@ -78,6 +78,55 @@ class AllowedResult:  # policy.go:93-125
         return self.ingress.is_allowed() and self.egress.is_allowed()
 
 
+class TargetEffects:
+    """Which target decides, per direction (cyc_probe_target_effects over a probe's whole table).
+
+    effects[direction]  int64 [T, slots, 4]: per target (primary-key order) and job slot, the cells where the
+                        target is in AllowingTargets / in DenyingTargets / the only allowing target beside a
+                        denying one / the only applying target, and denying (policy.go:84-96, 138-174)
+    applies[direction]  int64 [T]: the pods the target applies to (policy.go:68-82)
+    keys[direction]     the targets' primary keys, those of Policy.ingress / Policy.egress"""
+
+    DIRECTIONS = ("ingress", "egress")
+    KINDS = ("allowing", "denying", "sole_allowing", "sole_denying")
+
+    def __init__(self, keys, effects, applies):
+        self.keys, self.effects, self.applies = keys, effects, applies
+
+    def by_key(self, direction: str) -> dict:
+        """Primary key -> {"applies": pods, "allowing" / "denying" / "sole_allowing" / "sole_denying": [per slot]}."""
+        eff, app = self.effects[direction], self.applies[direction]
+        return {k: {"applies": int(app[i]), **{n: [int(v) for v in eff[i, :, e]] for e, n in enumerate(self.KINDS)}}
+                for i, k in enumerate(self.keys[direction])}
+
+    def _where(self, direction, mask):
+        return [k for k, m in zip(self.keys[direction], mask) if m]
+
+    def unused(self, direction: str) -> List[str]:
+        """Targets that apply to no pod."""
+        return self._where(direction, self.applies[direction] == 0)
+
+    def never_allowing(self, direction: str) -> List[str]:
+        """Targets that are in no cell's AllowingTargets."""
+        return self._where(direction, self.effects[direction][:, :, 0].sum(axis=1) == 0)
+
+    def redundant(self, direction: str) -> List[str]:
+        """Targets no verdict of this probe depends on alone: both sole counts are zero over all slots, so removing
+        the target changes nothing (targets that apply to no pod among them)."""
+        return self._where(direction, self.effects[direction][:, :, 2:].sum(axis=(1, 2)) == 0)
+
+    def render(self) -> str:
+        """A text table, targets in primary-key order, the counts summed over the slots."""
+        from .tablewriter import render
+
+        rows = []
+        for d in self.DIRECTIONS:
+            tot = self.effects[d].sum(axis=1)
+            for i, k in enumerate(self.keys[d]):
+                rows.append([d, k, int(self.applies[d][i])] + [int(v) for v in tot[i]])
+        return render(["Direction", "Target", "Applies to", "Allowing", "Denying", "Sole allowing", "Sole denying"], rows, True)
+
+
 class Policy:
     """*matcher.Policy: compiled targets held by a libcyclonus_hip context on `device`."""
 
@@ -95,6 +144,19 @@ class Policy:
     @property
     def egress(self) -> dict:
         return self.to_json()["Egress"]
+
+    def target_effects(self, probe_configs, resources) -> TargetEffects:
+        """Which target decides, over every job cell of the probe configs on `resources` (the cells of
+        Runner.run_probes' tables): one device computation per direction, no table needed."""
+        from .probe import _as_probe, _as_resources
+
+        eng = self.engine
+        eng.load_resources(json.dumps(_as_resources(resources).to_json()))
+        eng.prepare([_as_probe(c).to_json() for c in probe_configs])
+        ir = self.to_json()
+        keys = {d: list(ir[d.capitalize()] or {}) for d in TargetEffects.DIRECTIONS}
+        got = {d: eng.target_effects(d) for d in TargetEffects.DIRECTIONS}
+        return TargetEffects(keys, {d: g[0] for d, g in got.items()}, {d: g[1] for d, g in got.items()})
 
     def is_traffic_allowed(self, traffic) -> AllowedResult:
         """policy.go:131-136, with the allowing / denying target lists."""

@@ -261,6 +261,48 @@ int cyc_probe_run_rows(cyc_ctx* ctx, void* hip_stream, uint64_t* d_ingress, uint
 int cyc_probe_run_host_rows(cyc_ctx* ctx, uint64_t* ingress, uint64_t* egress, uint8_t* status, int partition,
                             int64_t row_lo, int64_t row_hi);
 
+/* ---- Which target decides: per-target effect counts over the verdict grid.
+ * For every cell the reference's Policy.IsIngressOrEgressAllowed (pkg/matcher/policy.go:138-174) sorts each
+ * target that applies to the cell's target pod into DirectionResult.AllowingTargets or .DenyingTargets
+ * (policy.go:84-96), and SimulatedJobRunner.RunJob renders that result per job (jobrunner.go:80).  The
+ * planes keep only the final bit; this call counts, per target t and job slot k, the cells of each kind
+ * without visiting them (bit rows of 64 pods).
+ *   direction  CYC_DIR_INGRESS counts over Policy.Ingress, CYC_DIR_EGRESS over Policy.Egress.  T below is
+ *              cyc_probe_shape.targets_in / targets_eg, and target index t is the primary-key order that
+ *              cyc_policy_ir_json and cyc_query_traffic_targets use.
+ *   rows       [row_lo, row_hi) are the pods the direction's policies TARGET: destinations for ingress,
+ *              sources for egress — cyc_probe_run's target rows, so the outputs of the shards of a row
+ *              partition add up to the whole table's.  The other end of a cell ranges over all P pods, a
+ *              pod's cell with itself included.
+ *   jobs       only VALID jobs count (status[d][k] == CYC_JOB_VALID, d the cell's destination): the
+ *              reference evaluates no policy for the other job kinds (jobrunner.go:36-55).
+ *   effects    host array, exactly T * nk * 4 elements written (nk = k_hi - k_lo); element
+ *              [(t*nk + k-k_lo)*4 + e] is the number of cells (s, d, k) of the range with
+ *                CYC_EFFECT_ALLOWING       t in AllowingTargets
+ *                CYC_EFFECT_DENYING        t in DenyingTargets
+ *                CYC_EFFECT_SOLE_ALLOWING  AllowingTargets == [t] and DenyingTargets is not empty: another
+ *                                          target applies and denies, so without t this direction's verdict
+ *                                          turns from allowed to blocked
+ *                CYC_EFFECT_SOLE_DENYING   DenyingTargets == [t] and AllowingTargets is empty: t is the only
+ *                                          target that applies, so without it the verdict turns to allowed
+ *                                          (policy.go:158-160)
+ *              SOLE_ALLOWING + SOLE_DENYING of t is therefore exactly the number of direction verdicts that
+ *              depend on t alone; a target with both zero over all slots can be removed without changing
+ *              any verdict of this probe.
+ *   applies    optional host array [T]: the pods of the rows t applies to (TargetsApplyingToPod,
+ *              policy.go:68-82).
+ * Needs cyc_probe_prepare or cyc_probe_prepare_configs and no run; synchronous; may be called at any time
+ * between runs.  It reads only what a prepare made and works in scratch it allocates and frees: the range
+ * plan, a captured graph, cyc_last_* and the options are as they were.  CYC_ERR_ARG (cyc_last_error names
+ * the problem): no prepare, a batched-blocks prepare, an unknown direction, a row or slot range out of
+ * bounds, NULL effects, and a problem with cyc_probe_shape.may_panic — take the panic from cyc_probe_run;
+ * the reference would die at its first such job.  An empty slot range, T == 0 and row_lo == row_hi are not
+ * errors: the (possibly zero) elements are written as zeros. */
+typedef enum { CYC_DIR_INGRESS = 0, CYC_DIR_EGRESS = 1 } cyc_direction;
+enum { CYC_EFFECT_ALLOWING = 0, CYC_EFFECT_DENYING = 1, CYC_EFFECT_SOLE_ALLOWING = 2, CYC_EFFECT_SOLE_DENYING = 3 };
+int cyc_probe_target_effects(cyc_ctx* ctx, int direction, int64_t row_lo, int64_t row_hi, int64_t k_lo, int64_t k_hi,
+                             int64_t* effects, int64_t* applies);
+
 /* ---- Device-resident verdict tables: the lazy probe.Table (pkg/connectivity/probe/table.go:24-56).
  * The reference's Runner.RunProbeForConfig returns *Table = NewTableFromJobResults(resources,
  * runProbe(jobs)) (jobrunner.go:29-58, table.go:38-48): one Item per (from, to) pod pair holding a
@@ -535,7 +577,9 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  * "class_inplace_active" and "emit_interleave_active" (the routes in effect; they need a run),
  * "plvt_active", "ip_iv_rows" and "ip_range_rows" (the current range plan's
  * interval-built and range-built IP rows); "pod_words" reports the mode the prepared probe uses (0 or 1; needs
- * cyc_probe_prepare). */
+ * cyc_probe_prepare).  Of the last cyc_probe_target_effects call it reports "effects_batches" (class batches),
+ * "effects_launches" (allow-row builds: one per batch and word window) and "effects_scratch_bytes" (device
+ * bytes it held at its peak), and "effects_scratch_cap" reports the bytes its batch buffers may take (256 MB). */
 int cyc_set_option(cyc_ctx* ctx, const char* name, int64_t value);
 int cyc_get_option(cyc_ctx* ctx, const char* name, int64_t* value);
 
