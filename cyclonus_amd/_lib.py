@@ -60,6 +60,8 @@ EXPORTS = [
     "cyc_table_compare_find",
     "cyc_table_group_counts",
     "cyc_table_group_compare",
+    "cyc_table_pod_counts",
+    "cyc_table_pod_compare",
     "cyc_table_shape",
     "cyc_table_error",
     "cyc_table_destroy",
@@ -105,6 +107,9 @@ EFFECTS = ("allowing", "denying", "sole_allowing", "sole_denying")
 # cyc_view (cyc_table_find)
 VIEW_INGRESS, VIEW_EGRESS, VIEW_COMBINED = 0, 1, 2
 VIEWS = {"ingress": VIEW_INGRESS, "egress": VIEW_EGRESS, "combined": VIEW_COMBINED}
+
+# CYC_POD_CODES: a row of cyc_table_pod_counts is the six cyc_connectivity codes, then the cells without a job
+POD_CODES = 7
 
 
 class CyclonusError(RuntimeError):
@@ -207,6 +212,8 @@ def lib():
         L.cyc_table_compare_find.argtypes = [vp, vp, i64, i64, i, i64, vp, i64, pi64, pi64, pi64]
         L.cyc_table_group_counts.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp]
         L.cyc_table_group_compare.argtypes = [vp, vp, vp, i64, i64, i64, i, vp, vp]
+        L.cyc_table_pod_counts.argtypes = [vp, i, i64, i64, vp, vp]
+        L.cyc_table_pod_compare.argtypes = [vp, vp, i64, i64, i, vp, vp, vp, vp]
         L.cyc_table_shape.argtypes = [vp, ctypes.POINTER(i64), i]
         L.cyc_table_error.argtypes = [vp]
         L.cyc_table_error.restype = cp

@@ -118,6 +118,27 @@ class ComparisonTable:
         """The per-job counts of value_counts_by_protocol, summed over the jobs, per pair of namespaces."""
         return self._by_namespace("slots", ignore_loopback)
 
+    def _by_pod(self, what: str, ignore_loopback: bool) -> dict:
+        """The cells sources' pod_compare (cyc_table_pod_compare on the device for DeviceTables):
+        {pod: {"as_source": {comparison: count}, "as_destination": {...}}}, zero counts left out."""
+        k = self.kube.slots
+        c = self.kube.src.pod_compare(self.simulated.src, k.start, k.stop, bool(ignore_loopback))
+        src, dst = c["src_" + what], c["dst_" + what]
+        if what == "slots":
+            src, dst = src.sum(axis=1), dst.sum(axis=1)
+        tally = lambda row: {x: int(n) for x, n in zip(COMPARISONS, row) if n}  # noqa: E731
+        return {p.pod_string(): {"as_source": tally(src[i]), "as_destination": tally(dst[i])}
+                for i, p in enumerate(self.kube.resources.pods)}
+
+    def value_counts_by_pod(self, ignore_loopback: bool = False) -> dict:
+        """value_counts (the (from, to) pairs) per pod, as the pairs' source and as their destination: where the
+        differences sit (an egress-side fault shows on the source, an ingress-side one on the destination)."""
+        return self._by_pod("pairs", ignore_loopback)
+
+    def job_counts_by_pod(self, ignore_loopback: bool = False) -> dict:
+        """The per-job counts of value_counts_by_protocol, summed over the jobs, per pod."""
+        return self._by_pod("slots", ignore_loopback)
+
     def different_jobs(self, ignore_loopback: bool, limit=None):
         """Yield (from, to, job key, kube Combined, simulated Combined) for every job counted as `different`
         (Item.ResultsByProtocol :14-20 under the loopback rule of :89-107), at most `limit` of them, in plane order

@@ -69,6 +69,13 @@ struct TileArgs {
   //          the differing pairs and whether the pair (d, d) differs
   unsigned long long* cnt;
   uint64_t* diff;  // compare, optional: [P][WA]
+  // The SRC instantiations (cyc_table_pod_counts, cyc_table_pod_compare) also count per source.  Source-minor for
+  // the same reason, source 64 * (w0 + j) + lane at [j * 64 + lane]:
+  // counts: [nk][WA * 64] allowed cells of `view` per (k, s)
+  // compare: [nk + 1][WA * 64]: differing cells per (k, s) where a holds a job (loopback left out when it is
+  //          ignored), then per s the differing pairs (whether (s, s) differs is cnt's entry of d = s)
+  unsigned long long* src_cnt;
+  uint32_t view;  // counts, SRC: cyc_view
 };
 
 // bits of word sw that are sources of the table (plane bits at or beyond s_hi are ignored)
@@ -77,17 +84,41 @@ __device__ __forceinline__ uint64_t source_mask(uint32_t sw, uint32_t s_hi) {
   return s_hi >= base + 64 ? ~0ull : s_hi > base ? (1ull << (s_hi - base)) - 1 : 0ull;
 }
 
-template <bool CMP>
+// Source words of a block's tile (the grid's y step): TT_WORDS, but half as many for the compare with SRC.
+constexpr uint32_t tile_source_words(bool cmp, bool src) { return cmp && src ? TT_WORDS / 2 : TT_WORDS; }
+
+// SRC: the mirrored accumulation.  A tile's bits over (s, d) are summed over d per source: for the words the lanes
+// hold by destination (the ingress word, the compare's XOR word) that is one more transpose64 and a popcount with
+// lane = s; the raw egress word already lies that way.  The block's 16 waves hold 16 destination words of the same
+// 64 sources, so they first add into a u32 LDS table [source words][64] (lane-contiguous: no bank conflict; a
+// block's sum per source and slot is at most 1024) and once per slot wave j adds word j's 64 sums to the global
+// buffer: one 64-bit atomic per (block, slot, source), 512 contiguous bytes a wave.  Integer adds: the results are
+// exact and the same from run to run.  The non-SRC instantiations compile to the code they had before SRC existed.
+template <bool CMP, bool SRC = false>
 __global__ __launch_bounds__(1024) void k_table_tiles(TileArgs a) {
+  // the block's source words: the compare holds 16 OR words, two tables' ingress words and two transposes in
+  // flight, and with the third transpose it spills at 16
+  constexpr uint32_t SW = tile_source_words(CMP, SRC);
+  __shared__ uint32_t src_acc[SRC ? TT_WORDS * 64 : 1];  // (a cell per thread: those of words past SW stay 0)
   const uint32_t lane = threadIdx.x & 63, dw = blockIdx.x * TT_WORDS + (threadIdx.x >> 6);
   // (a wave past the last destination word loads nothing and only keeps the block's barriers)
   const uint32_t d = dw * 64 + lane;
   const bool d_ok = dw < a.W && d < a.P;
-  const uint32_t sw0 = a.w0 + blockIdx.y * TT_WORDS, sw_end = min(sw0 + TT_WORDS, a.w0 + a.WA);
+  const uint32_t sw0 = a.w0 + blockIdx.y * SW, sw_end = min(sw0 + SW, a.w0 + a.WA);
   const uint64_t eg_step = uint64_t(64) * a.K * a.W;
-  uint64_t diff[TT_WORDS];
+  uint64_t diff[SW];
 #pragma unroll
-  for (uint32_t j = 0; j < TT_WORDS; j++) diff[j] = 0;
+  for (uint32_t j = 0; j < SW; j++) diff[j] = 0;
+  if (SRC) src_acc[threadIdx.x] = 0;  // (the first tile step's barrier stands between this and the adds)
+  // SRC, the end of a slot: the thread takes its cell of the table (wave j: source word sw0 + j) to slot `slot` of the
+  // buffer and clears it; the next tile step's barrier stands between that and the next adds.
+  auto drain_src = [&](uint32_t slot) {
+    __syncthreads();
+    const uint32_t n = src_acc[threadIdx.x], sw = sw0 + (threadIdx.x >> 6);
+    if (!n || sw >= sw_end) return;
+    src_acc[threadIdx.x] = 0;
+    atomicAdd(&a.src_cnt[(uint64_t(slot) * a.WA + (sw - a.w0)) * 64 + lane], (unsigned long long)n);
+  };
   for (uint32_t kk = 0; kk < a.nk; kk++) {
     const uint32_t k = a.k_lo + kk;
     const uint8_t sa = d_ok ? a.a.status[uint64_t(d) * a.K + k] : uint8_t(CYC_JOB_NONE);
@@ -103,7 +134,7 @@ __global__ __launch_bounds__(1024) void k_table_tiles(TileArgs a) {
       const bool any_both = __ballot(both) != 0;
       uint64_t n = 0;
 #pragma unroll
-      for (uint32_t h = 0; h < TT_WORDS; h += TT_BATCH) {
+      for (uint32_t h = 0; h < SW; h += TT_BATCH) {
         // the lane's ingress words of TT_BATCH tiles, loaded back to back: they share a line, which is then
         // fetched once per batch instead of once per tile (a block's 1024 ingress lines do not stay in the L1
         // over a tile step)
@@ -130,28 +161,44 @@ __global__ __launch_bounds__(1024) void k_table_tiles(TileArgs a) {
           diff[h + j] |= x;
           if (a.ignore_loopback && sw == dw) x &= ~(1ull << lane);
           n += __popcll(x);
+          if (SRC) {
+            if (sa == CYC_JOB_NONE) x = 0;  // (per job: only cells where a holds one)
+            if (__ballot(x != 0) == 0) continue;
+            const uint32_t p = __popcll(transpose64(x, lane));
+            if (p) atomicAdd(&src_acc[(h + j) * 64 + lane], p);
+          }
         }
       }
       if (sa != CYC_JOB_NONE && n) atomicAdd(&a.cnt[uint64_t(kk) * a.P + d], (unsigned long long)n);
     } else {
       const bool valid = sa == CYC_JOB_VALID;
-      const bool any_valid = __ballot(valid) != 0;  // (status-only slots need no plane read)
+      const uint64_t vmask = __ballot(valid);  // the VALID destinations of the wave's word
+      const bool any_valid = vmask != 0;       // (status-only slots need no plane read)
       uint64_t ni = 0, ne = 0, nc = 0;
-      uint64_t iw[TT_WORDS];  // the lane's ingress words of the block's tiles: one line, loaded back to back
+      uint64_t iw[SW];  // the lane's ingress words of the block's tiles: one line, loaded back to back
 #pragma unroll
-      for (uint32_t j = 0; j < TT_WORDS; j++) iw[j] = valid && sw0 + j < sw_end ? a.a.in[in_at + j] : 0ull;
+      for (uint32_t j = 0; j < SW; j++) iw[j] = valid && sw0 + j < sw_end ? a.a.in[in_at + j] : 0ull;
 #pragma unroll
-      for (uint32_t j = 0; j < TT_WORDS; j++) {
+      for (uint32_t j = 0; j < SW; j++) {
         const uint32_t sw = sw0 + j;
         if (sw >= sw_end) continue;
         __syncthreads();  // the block's waves take a tile step together (its egress lines: header comment)
         if (!any_valid) continue;
-        const uint64_t t = transpose64(sw * 64 + lane < a.s_hi ? a.a.eg[eg_at + j * eg_step] : 0ull, lane);
+        const uint64_t e = sw * 64 + lane < a.s_hi ? a.a.eg[eg_at + j * eg_step] : 0ull;
+        const uint64_t t = transpose64(e, lane);
         if (valid) {
           const uint64_t m = source_mask(sw, a.s_hi), i = iw[j] & m;
           ni += __popcll(i);
           ne += __popcll(t & m);
           nc += __popcll(t & i);
+        }
+        if (SRC) {
+          // lane = s: e is 0 at or beyond s_hi, and so are those lanes of the transposed ingress words (masked above
+          // by source bit); iw is 0 in lanes that are not VALID, which leaves the bits of VALID d < P
+          const uint32_t p = a.view == CYC_VIEW_EGRESS ? __popcll(e & vmask)
+                                                       : __popcll(transpose64(iw[j] & source_mask(sw, a.s_hi), lane) &
+                                                                  (a.view == CYC_VIEW_INGRESS ? ~0ull : e));
+          if (p) atomicAdd(&src_acc[j * 64 + lane], p);
         }
       }
       if (valid) {
@@ -161,12 +208,24 @@ __global__ __launch_bounds__(1024) void k_table_tiles(TileArgs a) {
         if (nc) atomicAdd(o + 2 * uint64_t(a.P), (unsigned long long)nc);
       }
     }
+    if (SRC) drain_src(kk);
+  }
+  if (CMP && SRC) {
+    // the pairs per source: the transposed OR words (lanes that are no destination hold zeros)
+    __syncthreads();  // (the last slot's drain cleared the table)
+#pragma unroll
+    for (uint32_t j = 0; j < SW; j++) {
+      if (sw0 + j >= sw_end || __ballot(diff[j] != 0) == 0) continue;
+      const uint32_t p = __popcll(transpose64(diff[j], lane));
+      if (p) atomicAdd(&src_acc[j * 64 + lane], p);
+    }
+    drain_src(a.nk);
   }
   if (CMP && d_ok) {
     uint64_t pairs = 0;
     bool self = false;
 #pragma unroll
-    for (uint32_t j = 0; j < TT_WORDS; j++) {
+    for (uint32_t j = 0; j < SW; j++) {
       const uint32_t sw = sw0 + j;
       if (sw >= sw_end) continue;
       if (a.diff) a.diff[uint64_t(d) * a.WA + (sw - a.w0)] = diff[j];  // (this wave owns the word)

@@ -954,7 +954,9 @@ static TileArgs tile_args(const cyc_table* t, int64_t k_lo, int64_t k_hi) {
   return a;
 }
 
-static dim3 tile_grid(const cyc_table* t) { return dim3((t->W + TT_WORDS - 1) / TT_WORDS, (t->wa + TT_WORDS - 1) / TT_WORDS); }
+static dim3 tile_grid(const cyc_table* t, uint32_t source_words = TT_WORDS) {
+  return dim3((t->W + TT_WORDS - 1) / TT_WORDS, (t->wa + source_words - 1) / source_words);
+}
 
 int cyc_table_counts(cyc_table* t, int64_t k_lo, int64_t k_hi, int64_t* ingress, int64_t* egress, int64_t* combined,
                      int64_t* no_job) {
@@ -1055,6 +1057,140 @@ int cyc_table_counts(cyc_table* t, int64_t k_lo, int64_t k_hi, int64_t* ingress,
   });
 }
 
+int cyc_table_pod_counts(cyc_table* t, int view, int64_t k_lo, int64_t k_hi, int64_t* by_src, int64_t* by_dst) {
+  if (!t) return CYC_ERR_ARG;
+  auto bad = [&](const char* m) {
+    t->err = m;
+    return (int)CYC_ERR_ARG;
+  };
+  if (view != CYC_VIEW_INGRESS && view != CYC_VIEW_EGRESS && view != CYC_VIEW_COMBINED) return bad("unknown view");
+  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
+  if (!by_src && !by_dst) return bad("no output requested");
+  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
+  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
+  if (!nk || !P) return (int)CYC_OK;
+  return table_guarded(t, [&]() -> int {
+    DeviceGuard dg(t->device);
+    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    // allowed cells per (slot, destination) of the three views (cyc_table_counts), and with by_src per (slot,
+    // source) of `view`
+    const int64_t src_stride = int64_t(t->wa) * 64;  // (TileArgs::src_cnt: source-minor)
+    const uint64_t n_cnt = uint64_t(nk) * 3 * P, n_src = by_src ? uint64_t(nk) * src_stride : 0;
+    std::vector<unsigned long long> cnt(n_cnt, 0), src(n_src, 0);
+    std::vector<uint8_t> st(size_t(P) * K);
+    DevBuf d_cnt;
+    if (rows) {
+      d_cnt.alloc((n_cnt + n_src) * 8);
+      HIPCHK(hipMemsetAsync(d_cnt.p, 0, (n_cnt + n_src) * 8, t->stream));
+      TileArgs a = tile_args(t, k_lo, k_hi);
+      a.cnt = d_cnt.as<unsigned long long>();
+      a.src_cnt = a.cnt + n_cnt;
+      a.view = uint32_t(view);
+      if (by_src) k_table_tiles<false, true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
+      else k_table_tiles<false><<<tile_grid(t), 1024, 0, t->stream>>>(a);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(cnt.data(), a.cnt, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
+      if (n_src) HIPCHK(hipMemcpyAsync(src.data(), a.src_cnt, n_src * 8, hipMemcpyDeviceToHost, t->stream));
+    }
+    HIPCHK(hipMemcpyAsync(st.data(), t->status, st.size(), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    // the status-only terms, as cyc_table_counts': the code of a destination's slot that is not VALID holds for
+    // every source, so a source's row has as many cells of it as there are such destinations
+    const int inv_np = view == CYC_VIEW_EGRESS ? CYC_CONN_UNKNOWN : CYC_CONN_INVALID_NAMED_PORT;
+    const int inv_pp = view == CYC_VIEW_EGRESS ? CYC_CONN_UNKNOWN : CYC_CONN_INVALID_PORT_PROTOCOL;
+    for (int64_t kk = 0; kk < nk; kk++) {
+      int64_t n_of[4] = {0, 0, 0, 0};  // destinations per cyc_job_status
+      for (int64_t d = 0; d < P; d++) {
+        const uint8_t s = st[size_t(d * K + k_lo + kk)];
+        n_of[s <= CYC_JOB_BAD_PORT_PROTOCOL ? s : CYC_JOB_BAD_NAMED_PORT]++;  // (any other value: as cyc_table_counts)
+        if (!by_dst) continue;
+        int64_t* o = by_dst + (d * nk + kk) * CYC_POD_CODES;
+        for (int c = 0; c < CYC_POD_CODES; c++) o[c] = 0;
+        if (s == CYC_JOB_VALID) {
+          const int64_t a = int64_t(cnt[size_t((kk * 3 + view) * P + d)]);
+          o[CYC_CONN_ALLOWED] = a, o[CYC_CONN_BLOCKED] = rows - a;
+        } else {
+          o[s == CYC_JOB_NONE ? 6 : s == CYC_JOB_BAD_PORT_PROTOCOL ? inv_pp : inv_np] = rows;
+        }
+      }
+      for (int64_t i = 0; by_src && i < rows; i++) {
+        int64_t* o = by_src + (i * nk + kk) * CYC_POD_CODES;
+        for (int c = 0; c < CYC_POD_CODES; c++) o[c] = 0;
+        const int64_t a = int64_t(src[size_t(kk * src_stride + i)]);
+        o[CYC_CONN_ALLOWED] = a, o[CYC_CONN_BLOCKED] = n_of[CYC_JOB_VALID] - a;
+        o[inv_np] += n_of[CYC_JOB_BAD_NAMED_PORT], o[inv_pp] += n_of[CYC_JOB_BAD_PORT_PROTOCOL];
+        o[6] = n_of[CYC_JOB_NONE];
+      }
+    }
+    return (int)CYC_OK;
+  });
+}
+
+// What cyc_table_compare and cyc_table_pod_compare check alike; nullptr when the arguments are fine.
+static const char* compare_args_bad(const cyc_table* ta, const cyc_table* tb, int64_t k_lo, int64_t k_hi) {
+  if (!tb) return "null table";
+  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition ||
+      ta->row_lo != tb->row_lo || ta->row_hi != tb->row_hi)
+    return "cannot compare tables of different devices, shapes, partitions or rows";
+  if (k_lo < 0 || k_hi > int64_t(ta->K) || k_lo > k_hi) return "slot range out of bounds";
+  if (!table_whole(ta)) return "ingress cells need destinations inside the table's rows";
+  return nullptr;
+}
+
+// The compare pass over the tiles and what the host needs of it: the kernel's per-destination buffer (TileArgs::cnt),
+// with `src` its per-source buffer (TileArgs::src_cnt) too, and a's status plane.  Zeros where the table has no cell.
+struct CompareTiles {
+  std::vector<unsigned long long> cnt, src;
+  std::vector<uint8_t> sa;
+};
+static CompareTiles compare_tiles(cyc_table* t, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, uint64_t* d_diff,
+                                  bool src) {
+  const uint64_t nk = uint64_t(k_hi - k_lo), P = t->P, n_cnt = P * (nk + 2), n_src = src ? (nk + 1) * t->wa * 64 : 0;
+  CompareTiles r;
+  r.cnt.assign(n_cnt, 0), r.src.assign(n_src, 0), r.sa.assign(size_t(P) * t->K, 0);
+  if (!P || t->row_hi == t->row_lo) return r;
+  if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+  DevBuf d_cnt;
+  d_cnt.alloc((n_cnt + n_src) * 8);
+  HIPCHK(hipMemsetAsync(d_cnt.p, 0, (n_cnt + n_src) * 8, t->stream));
+  TileArgs a = tile_args(t, k_lo, k_hi);
+  a.b = TablePlanes{tb->in, tb->eg, tb->status};
+  a.ignore_loopback = ignore_loopback ? 1u : 0u;
+  a.cnt = d_cnt.as<unsigned long long>();
+  a.src_cnt = a.cnt + n_cnt;
+  a.diff = d_diff;
+  if (src) k_table_tiles<true, true><<<tile_grid(t, tile_source_words(true, true)), 1024, 0, t->stream>>>(a);
+  else k_table_tiles<true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(r.cnt.data(), a.cnt, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
+  if (n_src) HIPCHK(hipMemcpyAsync(r.src.data(), a.src_cnt, n_src * 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(r.sa.data(), t->status, r.sa.size(), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));  // (d_cnt is freed after it)
+  return r;
+}
+
+// per job (ValueCountsByProtocol :89-107, ResultsByProtocol :14-20,69-79): every cell whose job a holds, summed
+// (slot_counts) and per destination (dst_counts), each optional
+static void compare_jobs_by_dst(const cyc_table* t, const CompareTiles& r, int64_t k_lo, int64_t nk, int ignore_loopback,
+                                int64_t* slot_counts, int64_t* dst_counts) {
+  const int64_t P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
+  for (int64_t i = 0; slot_counts && i < nk * 3; i++) slot_counts[i] = 0;
+  if (slot_counts || dst_counts)
+    for (int64_t d = 0; d < P; d++)
+      for (int64_t kk = 0; kk < nk; kk++) {
+        int64_t v[3] = {0, 0, 0};
+        if (r.sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE) {
+          v[2] = ignore_loopback && d >= t->row_lo && d < t->row_hi ? 1 : 0;
+          v[1] = int64_t(r.cnt[size_t(kk * P + d)]);
+          v[0] = rows - v[1] - v[2];
+        }
+        for (int x = 0; x < 3; x++) {
+          if (slot_counts) slot_counts[kk * 3 + x] += v[x];
+          if (dst_counts) dst_counts[(d * nk + kk) * 3 + x] = v[x];
+        }
+      }
+}
+
 int cyc_table_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t pair_counts[3],
                       int64_t* slot_counts, int64_t* dst_counts, uint64_t* d_diff) {
   if (!ta) return CYC_ERR_ARG;
@@ -1065,35 +1201,13 @@ int cyc_table_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, 
   };
   if (!tb) return bad("null table");
   if (!pair_counts) return bad("null pair_counts");
-  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition ||
-      ta->row_lo != tb->row_lo || ta->row_hi != tb->row_hi)
-    return bad("cannot compare tables of different devices, shapes, partitions or rows");
-  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
-  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
+  if (const char* why = compare_args_bad(ta, tb, k_lo, k_hi)) return bad(why);
   if (reinterpret_cast<uintptr_t>(d_diff) % 8) return bad("d_diff is not 8-byte aligned");
-  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
+  const int64_t nk = k_hi - k_lo, P = t->P, rows = t->row_hi - t->row_lo;
   return table_guarded(t, [&]() -> int {
     DeviceGuard dg(t->device);
-    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    const uint64_t per = uint64_t(nk) + 2, n_cnt = uint64_t(P) * per;
-    std::vector<unsigned long long> cnt(n_cnt, 0);
-    std::vector<uint8_t> sa(size_t(P) * K), sb(size_t(P) * K);
-    if (P && rows) {
-      DevBuf d_cnt;
-      d_cnt.alloc(n_cnt * 8);
-      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
-      TileArgs a = tile_args(t, k_lo, k_hi);
-      a.b = TablePlanes{tb->in, tb->eg, tb->status};
-      a.ignore_loopback = ignore_loopback ? 1u : 0u;
-      a.cnt = d_cnt.as<unsigned long long>();
-      a.diff = d_diff;
-      k_table_tiles<true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipMemcpyAsync(sa.data(), ta->status, sa.size(), hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipMemcpyAsync(sb.data(), tb->status, sb.size(), hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipStreamSynchronize(t->stream));  // (d_cnt is freed after it)
-    }
+    const CompareTiles r = compare_tiles(t, tb, k_lo, k_hi, ignore_loopback, d_diff, false);
+    const std::vector<unsigned long long>& cnt = r.cnt;
     // ValueCounts (comparisontable.go:109-123): a pair is the Items' equalsDict (:26-36) unless it is an
     // ignored loopback; the table answers the pairs (s in its rows, every d)
     int64_t differ = 0, self_differ = 0;
@@ -1101,22 +1215,54 @@ int cyc_table_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, 
     pair_counts[2] = ignore_loopback ? rows : 0;
     pair_counts[1] = differ - (ignore_loopback ? self_differ : 0);
     pair_counts[0] = rows * P - pair_counts[1] - pair_counts[2];
-    // per job (ValueCountsByProtocol :89-107, ResultsByProtocol :14-20,69-79): every cell whose job a holds
-    for (int64_t i = 0; slot_counts && i < nk * 3; i++) slot_counts[i] = 0;
-    if (slot_counts || dst_counts)
-      for (int64_t d = 0; d < P; d++)
-        for (int64_t kk = 0; kk < nk; kk++) {
-          int64_t v[3] = {0, 0, 0};
-          if (sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE) {
-            v[2] = ignore_loopback && d >= t->row_lo && d < t->row_hi ? 1 : 0;
-            v[1] = int64_t(cnt[size_t(kk * P + d)]);
-            v[0] = rows - v[1] - v[2];
-          }
-          for (int x = 0; x < 3; x++) {
-            if (slot_counts) slot_counts[kk * 3 + x] += v[x];
-            if (dst_counts) dst_counts[(d * nk + kk) * 3 + x] = v[x];
-          }
-        }
+    compare_jobs_by_dst(t, r, k_lo, nk, ignore_loopback, slot_counts, dst_counts);
+    return (int)CYC_OK;
+  });
+}
+
+int cyc_table_pod_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t* src_pairs,
+                          int64_t* dst_pairs, int64_t* src_slots, int64_t* dst_slots) {
+  if (!ta) return CYC_ERR_ARG;
+  cyc_table* t = ta;
+  auto bad = [&](const char* m) {
+    t->err = m;
+    return (int)CYC_ERR_ARG;
+  };
+  if (const char* why = compare_args_bad(ta, tb, k_lo, k_hi)) return bad(why);
+  if (!src_pairs && !dst_pairs && !src_slots && !dst_slots) return bad("no output requested");
+  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo, il = ignore_loopback ? 1 : 0;
+  return table_guarded(t, [&]() -> int {
+    DeviceGuard dg(t->device);
+    const CompareTiles r = compare_tiles(t, tb, k_lo, k_hi, ignore_loopback, nullptr, src_pairs || src_slots);
+    const unsigned long long* self = r.cnt.data() + (nk + 1) * P;  // whether the pair (d, d) differs
+    // the pairs (ValueCounts, as cyc_table_compare): of destination d over the table's sources, of source s over
+    // every destination; the loopback pair is ignored whether it differs or not
+    for (int64_t d = 0; dst_pairs && d < P; d++) {
+      int64_t* o = dst_pairs + d * 3;
+      o[2] = il && d >= t->row_lo && d < t->row_hi ? 1 : 0;
+      o[1] = int64_t(r.cnt[size_t(nk * P + d)]) - (il ? int64_t(self[d]) : 0);
+      o[0] = rows - o[1] - o[2];
+    }
+    const int64_t src_stride = int64_t(t->wa) * 64;  // (TileArgs::src_cnt: source-minor)
+    for (int64_t i = 0; src_pairs && i < rows; i++) {
+      int64_t* o = src_pairs + i * 3;
+      o[2] = il;
+      o[1] = int64_t(r.src[size_t(nk * src_stride + i)]) - (il ? int64_t(self[t->row_lo + i]) : 0);
+      o[0] = P - o[1] - o[2];
+    }
+    compare_jobs_by_dst(t, r, k_lo, nk, ignore_loopback, nullptr, dst_slots);
+    // per job and source: a's jobs of slot kk are the destinations whose status is not NONE, the loopback cell is
+    // ignored when (s, kk) is a job of a
+    for (int64_t kk = 0; src_slots && kk < nk; kk++) {
+      int64_t jobs = 0;
+      for (int64_t d = 0; d < P; d++) jobs += r.sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE;
+      for (int64_t i = 0; i < rows; i++) {
+        int64_t* o = src_slots + (i * nk + kk) * 3;
+        o[2] = il && r.sa[size_t((t->row_lo + i) * K + k_lo + kk)] != CYC_JOB_NONE ? 1 : 0;
+        o[1] = int64_t(r.src[size_t(kk * src_stride + i)]);
+        o[0] = jobs - o[1] - o[2];
+      }
+    }
     return (int)CYC_OK;
   });
 }

@@ -324,7 +324,8 @@ class Engine:
 
 class DeviceTable:
     """A cyc_table: verdict planes resident on the GPU; cells() returns probe.Connectivity codes, counts()
-    and compare() the whole-table summaries, find() and compare_find() the cells behind them as records in
+    and compare() the whole-table summaries, group_counts() / group_compare() and pod_counts() / pod_compare() the
+    same per pair of pod groups and per pod, find() and compare_find() the cells behind them as records in
     (s, d, k) order (all computed on the device)."""
 
     def __init__(self, handle: ctypes.c_void_p, device: int = 0):
@@ -430,6 +431,31 @@ class DeviceTable:
         out = {"pairs": np.zeros(shape[:2] + (3,), np.int64), "slots": np.zeros(shape + (3,), np.int64)}
         self._check(lib().cyc_table_group_compare(self._t, other._t, g.ctypes.data, G, int(k_lo), int(k_hi), int(bool(ignore_loopback)),
                                                   out["pairs"].ctypes.data, out["slots"].ctypes.data))
+        return out
+
+    def pod_counts(self, view, k_lo=0, k_hi=None, want=("src", "dst")):
+        """cyc_table_pod_counts: {"src": i64 [rows, k, 7], "dst": i64 [P, k, 7]}: per source of the table's rows
+        (over every destination) and per destination (over those sources) the cells of slots [k_lo, k_hi) per
+        cyc_connectivity code in `view` ("ingress", "egress", "combined" or a cyc_view); column 6: cells without a job."""
+        k_hi = self.slots if k_hi is None else k_hi
+        nk = max(k_hi - k_lo, 0)
+        n = {"src": self.row_hi - self.row_lo, "dst": self.pods}
+        out = {x: np.zeros((n[x], nk, _lib.POD_CODES), np.int64) for x in want}
+        # (empty numpy arrays still have a data pointer: an empty output is never the NULL the library refuses)
+        ptr = [ctypes.c_void_p(out[x].ctypes.data) if x in out else None for x in ("src", "dst")]
+        self._check(lib().cyc_table_pod_counts(self._t, int(_lib.VIEWS.get(view, view)), int(k_lo), int(k_hi), *ptr))
+        return out
+
+    def pod_compare(self, other: "DeviceTable", k_lo=0, k_hi=None, ignore_loopback=False):
+        """cyc_table_pod_compare(self, other): compare per pod, (same, different, ignored) last: {"src_pairs": i64
+        [rows, 3], "dst_pairs": i64 [P, 3]} the (from, to) pairs of a source and of a destination, {"src_slots": i64
+        [rows, k, 3], "dst_slots": i64 [P, k, 3]} the per-job counts (dst_slots is compare's "dst")."""
+        k_hi = self.slots if k_hi is None else k_hi
+        nk, rows = max(k_hi - k_lo, 0), self.row_hi - self.row_lo
+        out = {"src_pairs": np.zeros((rows, 3), np.int64), "dst_pairs": np.zeros((self.pods, 3), np.int64),
+               "src_slots": np.zeros((rows, nk, 3), np.int64), "dst_slots": np.zeros((self.pods, nk, 3), np.int64)}
+        self._check(lib().cyc_table_pod_compare(self._t, other._t, int(k_lo), int(k_hi), int(bool(ignore_loopback)),
+                                                *(ctypes.c_void_p(out[x].ctypes.data) for x in ("src_pairs", "dst_pairs", "src_slots", "dst_slots"))))
         return out
 
     def _find(self, call, k_lo, k_hi, s_from, cap, out):

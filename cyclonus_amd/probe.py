@@ -277,6 +277,51 @@ class PlaneCells:
                 np.add.at(pairs, (gs[m], gd[m], x), 1)
         return {"pairs": pairs, "slots": slots}
 
+    # The pod level (cyc_table_pod_counts / cyc_table_pod_compare), cell by cell: what DeviceTable.pod_counts /
+    # pod_compare are tested against.
+    def pod_counts(self, view, k_lo=0, k_hi=None, want=("src", "dst")):
+        """cyc_table_pod_counts: {"src": i64 [P, k, 7], "dst": i64 [P, k, 7]} cells per (source, slot, code) over
+        every destination and per (destination, slot, code) over every source; column 6: cells without a job."""
+        view = {v: n for n, v in _lib.VIEWS.items()}.get(view, view)
+        if view not in _lib.VIEWS:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "unknown view")
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        P, chunks = self._source_chunks()
+        nk = max(k_hi - k_lo, 0)
+        out = {"src": np.zeros((P, nk, _lib.POD_CODES), np.int64), "dst": np.zeros((P, nk, _lib.POD_CODES), np.int64)}
+        for lo, hi in chunks:
+            codes = self.cells(lo, hi, 0, P, k_lo, k_hi, want=(view,))[view]
+            for c in range(_lib.POD_CODES):
+                m = codes == (c if c < 6 else _lib.CONN_NO_JOB)
+                out["src"][lo:hi, :, c] = m.sum(axis=1)
+                out["dst"][:, :, c] += m.sum(axis=0)
+        return {n: out[n] for n in want}
+
+    def pod_compare(self, other, k_lo=0, k_hi=None, ignore_loopback=False):
+        """cyc_table_pod_compare(self, other): {"src_pairs": [P, 3], "dst_pairs": [P, 3], "src_slots": [P, k, 3],
+        "dst_slots": [P, k, 3]} in (same, different, ignored) order: compare's pairs and per-job counts by pod."""
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        if other.status.shape != self.status.shape:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "cannot compare tables of different devices, shapes, partitions or rows")
+        P, chunks = self._source_chunks()
+        nk = max(k_hi - k_lo, 0)
+        out = {"src_pairs": np.zeros((P, 3), np.int64), "dst_pairs": np.zeros((P, 3), np.int64),
+               "src_slots": np.zeros((P, nk, 3), np.int64), "dst_slots": np.zeros((P, nk, 3), np.int64)}
+        for lo, hi in chunks:
+            ca = self.cells(lo, hi, 0, P, k_lo, k_hi, want=("combined",))["combined"]
+            cb = other.cells(lo, hi, 0, P, k_lo, k_hi, want=("combined",))["combined"]
+            loopback = (np.arange(lo, hi)[:, None] == np.arange(P)[None, :]) & bool(ignore_loopback)
+            job = ca != _lib.CONN_NO_JOB  # every job of the kube Item, once
+            ignored = job & loopback[:, :, None]
+            for x, m in enumerate((job & ~ignored & (ca == cb), job & ~ignored & (ca != cb), ignored)):
+                out["src_slots"][lo:hi, :, x] = m.sum(axis=1)
+                out["dst_slots"][:, :, x] += m.sum(axis=0)
+            item_differs = (ca != cb).any(axis=2)  # equalsDict over the job keys, NO_JOB included
+            for x, m in enumerate((~loopback & ~item_differs, ~loopback & item_differs, loopback)):
+                out["src_pairs"][lo:hi, x] = m.sum(axis=1)
+                out["dst_pairs"][:, x] += m.sum(axis=0)
+        return out
+
     # The listings (cyc_table_find / cyc_table_compare_find), cell by cell: the same contract as
     # DeviceTable.find / compare_find, which are tested against this restatement.
     def _page(self, matcher, k_lo, k_hi, s_from, cap):
@@ -464,6 +509,25 @@ class Table:
         counts = self.namespace_counts(view)
         rows = [[fr] + [f"{counts[fr, to].get(ALLOWED, 0)}/{sum(counts[fr, to].values())}" for to in names] for fr in names]
         return render([""] + names, rows, row_line=False)
+
+    # The pod level: which pods reach everything or nothing, which are reached from everywhere.
+    def pod_counts(self, view: str = "combined") -> dict:
+        """{pod: {"as_source": {Connectivity: jobs}, "as_destination": {Connectivity: jobs}}} over the table's slots
+        for the jobs' Ingress, Egress or Combined (`view`): the jobs from the pod to every pod and from every pod to it,
+        zero counts left out; counted by the cells source (cyc_table_pod_counts on the device for a DeviceTable)."""
+        if view not in _lib.VIEWS:
+            raise ValueError(f"invalid view: {view}")
+        c = self.src.pod_counts(view, self.slots.start, self.slots.stop)
+        src, dst = c["src"].sum(axis=1), c["dst"].sum(axis=1)
+        tally = lambda row: {_CONN[x]: int(row[x]) for x in range(6) if row[x]}  # noqa: E731
+        return {p.pod_string(): {"as_source": tally(src[i]), "as_destination": tally(dst[i])} for i, p in enumerate(self.resources.pods)}
+
+    def render_pod_table(self, view: str = "combined") -> str:
+        """A row per pod in sorted-name order: "<allowed jobs>/<jobs>" as source and as destination."""
+        counts = self.pod_counts(view)
+        cell = lambda c: f"{c.get(ALLOWED, 0)}/{sum(c.values())}"  # noqa: E731
+        rows = [[name, cell(counts[name]["as_source"]), cell(counts[name]["as_destination"])] for name in self.items]
+        return render(["", "as source", "as destination"], rows, row_line=False)
 
     # table.go:58-156
     def render_ingress(self) -> str:

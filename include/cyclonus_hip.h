@@ -441,6 +441,38 @@ int cyc_table_group_counts(cyc_table* t, const int32_t* group_of, int64_t n_grou
  * When no pod is -1 the sums over (gs, gd) are cyc_table_compare's pair_counts and slot_counts. */
 int cyc_table_group_compare(cyc_table* a, cyc_table* b, const int32_t* group_of, int64_t n_groups, int64_t k_lo,
                             int64_t k_hi, int ignore_loopback, int64_t* pair_counts, int64_t* slot_counts);
+/* ---- The pod level: counts and comparison per source pod and per destination pod (which pods reach everything
+ * or nothing; on which pods the differences of two tables sit: an egress-side fault shows per source, an
+ * ingress-side one per destination).  The reference has no such summary.  Accepted tables as for cyc_table_find
+ * (a partial target-row table is refused); stream, lifetime, failures, plane bits at or beyond P and plane
+ * alignment as for cyc_table_counts: one pass over the planes.  Below rows = row_hi - row_lo, nk = k_hi - k_lo,
+ * r = s - row_lo.  Exactly the stated number of elements of each output array is written.
+ *
+ * view: a cyc_view.  Column c of a row of 7: c in 0..5 the cells with cyc_connectivity code c in that view (the
+ * codes of cyc_table_cells), [6] the cells without a job (CYC_CONN_NO_JOB).  Outputs (host, each optional, at
+ * least one):
+ *   by_src  [(r * nk + k - k_lo) * 7 + c]: for source s of the table's rows, the destinations d in [0, P) whose
+ *           cell (s, d, k) has that code; every (r, k) row sums to P.
+ *   by_dst  [(d * nk + k - k_lo) * 7 + c]: for every destination d in [0, P), the sources of the table's rows;
+ *           every (d, k) row sums to rows.
+ * Summed over the pods, the columns 0..5 of either array are cyc_table_counts' result for that view and the sum
+ * of column 6 is its no_job.  The by_dst of a source partition's shards add up to the whole table's; their by_src
+ * are its rows [row_lo, row_hi).  A bad view or slot range, both outputs NULL: CYC_ERR_ARG.  An empty slot range
+ * writes nothing; rows == 0 writes by_dst's zeros. */
+#define CYC_POD_CODES 7 /* cyc_connectivity 0..5, then [6] = cells without a job (CYC_CONN_NO_JOB) */
+int cyc_table_pod_counts(cyc_table* t, int view /* cyc_view */, int64_t k_lo, int64_t k_hi, int64_t* by_src,
+                         int64_t* by_dst);
+/* cyc_table_compare per pod (a and b must match as there; no d_diff).  Each output (host, optional, at least
+ * one) is {same, different, ignored} under cyc_table_compare's rules:
+ *   src_pairs  [r * 3 + x]: the pairs (from = s, to = d) over every d; ignored iff ignore_loopback and s == d.
+ *   dst_pairs  [d * 3 + x]: the pairs over the sources of the table's rows (an ignored pair only when d is one).
+ *   src_slots  [(r * nk + k - k_lo) * 3 + x]: per job as slot_counts (only cells where a holds a job, loopback
+ *              tested before success, a job b lacks is different), over every d.
+ *   dst_slots  [(d * nk + k - k_lo) * 3 + x]: element for element cyc_table_compare's dst_counts.
+ * Summed over the pods, src_pairs and dst_pairs are cyc_table_compare's pair_counts, src_slots and dst_slots its
+ * slot_counts. */
+int cyc_table_pod_compare(cyc_table* a, cyc_table* b, int64_t k_lo, int64_t k_hi, int ignore_loopback,
+                          int64_t* src_pairs, int64_t* dst_pairs, int64_t* src_slots, int64_t* dst_slots);
 /* out[0..7] = pods, slots, words, row_lo, row_hi, partition, ingress window first word, window words */
 int cyc_table_shape(const cyc_table* t, int64_t* out, int n);
 const char* cyc_table_error(const cyc_table* t);

@@ -1,9 +1,10 @@
 """Config #3's whole table through cyc_table_counts and cyc_table_compare, against a plain read of the same planes.
 
     python scripts/table_counts_bench.py time [reps=3] [out=FILE]   # the table below, as text and one JSON line
-    python scripts/table_counts_bench.py run counts|compare|find_count|compare_find|find_dense|group_counts|group_compare [n=2]
-                                                                    # n calls of one pass (for a rocprofv3 run)
+    python scripts/table_counts_bench.py run counts|compare|find_count|compare_find|find_dense|group_counts|group_compare|
+                                             pod_counts|pod_compare [n=2]   # n calls of one pass (for a rocprofv3 run)
     python scripts/table_counts_bench.py group [reps=3] [out=FILE]  # the group leg alone (below)
+    python scripts/table_counts_bench.py pod [reps=3] [out=FILE]    # the pod leg alone (below)
 
 In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
 drawn with another seed; then, min over reps of the synchronous calls,
@@ -21,6 +22,13 @@ ungrouped counterparts on the same tables, min over reps of each:
   group_counts   cyc_table_group_counts, all three views and no_job, against cyc_table_counts; and Combined alone
   group_compare  cyc_table_group_compare with slot_counts against cyc_table_compare without d_diff
 and once, as checks, that the group results summed over the group pairs are the ungrouped results.
+The pod leg (mode `pod`): every slot, interleaved with their whole-table counterparts on the same tables, min over
+reps of each:
+  pod_counts   cyc_table_pod_counts(Combined), both outputs, against cyc_table_counts; and by_dst alone, which
+               launches the kernel cyc_table_counts launches
+  pod_compare  cyc_table_pod_compare, all four outputs, against cyc_table_compare without d_diff
+and once, as checks, the sum invariants: both arrays of either call summed over the pods are the whole-table results,
+and dst_slots is cyc_table_compare's dst_counts.
 """
 import json
 import os
@@ -104,6 +112,8 @@ groups = np.array([ns_at[p["Namespace"]] for p in data["resources"]["Pods"]], np
 G = len(names)
 GROUP = {"group_counts": lambda: ta.group_counts(groups, G), "group_compare": lambda: ta.group_compare(tb, groups, G, ignore_loopback=True)}
 
+POD = {"pod_counts": lambda: ta.pod_counts("combined"), "pod_compare": lambda: ta.pod_compare(tb, ignore_loopback=True)}
+
 tc = flipped[0]
 page = np.zeros(P * K, CELL_DTYPE)  # cap = P * K always makes progress
 LISTINGS = {
@@ -113,7 +123,7 @@ LISTINGS = {
 }
 
 if mode == "run":
-    f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS, **GROUP}[pos[0]]
+    f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS, **GROUP, **POD}[pos[0]]
     for _ in range(n_run):
         f()
     sys.exit(0)
@@ -146,6 +156,45 @@ if mode == "group":
         f"(compare without d_diff; host outputs {res['group_compare_out_mb']:.0f} MB)",
         f"group results summed over the group pairs equal the ungrouped results: {sums_ok}; namespace pairs with an allowed Combined cell "
         f"{res['group_pairs_with_allowed']} of {G * G}, that differ between the tables {res['group_pairs_that_differ']}",
+        json.dumps(res),
+    ]
+    print("\n".join(lines))
+    if "out" in kw:
+        os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
+        with open(kw["out"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
+
+if mode == "pod":
+    legs = {"counts": lambda: ta.counts(), "pod_counts": POD["pod_counts"], "pod_counts_dst": lambda: ta.pod_counts("combined", want=("dst",)),
+            "compare_nodiff": lambda: ta.compare(tb, ignore_loopback=True), "pod_compare": POD["pod_compare"]}
+    pc, pp = POD["pod_counts"](), POD["pod_compare"]()  # (warm-up, and the checks)
+    c, r = ta.counts(), ta.compare(tb, ignore_loopback=True)
+    sums_ok = (all(np.array_equal(pc[n][:, :, :6].sum(axis=0), c["combined"]) and int(pc[n][:, :, 6].sum()) == c["no_job"] for n in ("src", "dst"))
+               and all(np.array_equal(pp[n + "_pairs"].sum(axis=0), r["pairs"]) and np.array_equal(pp[n + "_slots"].sum(axis=0), r["slots"])
+                       for n in ("src", "dst")) and np.array_equal(pp["dst_slots"], r["dst"]))
+    ms = {n: float("inf") for n in legs}
+    for _ in range(reps):  # interleaved: every leg once per round
+        for n, f in legs.items():
+            ms[n] = min(ms[n], timed(f, 1))
+    reach_all = int((pc["src"][:, :, CONN_ALLOWED].sum(axis=1) == pc["src"][:, :, :6].sum(axis=(1, 2))).sum())
+    res = {"config": config, "pods": P, "slots": K, "words": W, "plane_gb": round(plane_gb, 3), "reps": reps,
+           **{n + "_ms": v for n, v in ms.items()}, "sums_equal_whole_table": bool(sums_ok),
+           "pod_counts_over_counts": ms["pod_counts"] / ms["counts"], "pod_counts_dst_over_counts": ms["pod_counts_dst"] / ms["counts"],
+           "pod_compare_over_compare": ms["pod_compare"] / ms["compare_nodiff"],
+           "pod_counts_out_mb": sum(a.nbytes for a in pc.values()) / 1e6, "pod_compare_out_mb": sum(a.nbytes for a in pp.values()) / 1e6,
+           "sources_that_reach_nothing": int((pc["src"][:, :, CONN_ALLOWED].sum(axis=1) == 0).sum()), "sources_that_reach_every_job": reach_all,
+           "sources_with_a_different_pair": int((pp["src_pairs"][:, 1] > 0).sum()),
+           "destinations_with_a_different_pair": int((pp["dst_pairs"][:, 1] > 0).sum())}
+    lines = [
+        f"# {config}: P {P}, K {K}, W {W}; a plane is {plane_gb:.2f} GB; min of {reps} interleaved synchronous calls",
+        f"counts         {ms['counts']:9.2f} ms   pod_counts(combined) {ms['pod_counts']:9.2f} ms  ratio {res['pod_counts_over_counts']:.2f}  "
+        f"(host outputs {res['pod_counts_out_mb']:.1f} MB; by_dst alone {ms['pod_counts_dst']:.2f} ms, ratio {res['pod_counts_dst_over_counts']:.2f})",
+        f"compare        {ms['compare_nodiff']:9.2f} ms   pod_compare          {ms['pod_compare']:9.2f} ms  ratio {res['pod_compare_over_compare']:.2f}  "
+        f"(compare without d_diff; host outputs {res['pod_compare_out_mb']:.1f} MB)",
+        f"sums over the pods equal counts / compare, dst_slots equals compare's dst: {sums_ok}; sources that reach nothing "
+        f"{res['sources_that_reach_nothing']}, that reach every job {reach_all}; pods with a different pair: "
+        f"{res['sources_with_a_different_pair']} as source, {res['destinations_with_a_different_pair']} as destination",
         json.dumps(res),
     ]
     print("\n".join(lines))
