@@ -1730,7 +1730,11 @@ int cyc_get_option(cyc_ctx* c, const char* name, int64_t* value) {
   } else if (n == "plvt_active") *value = c->prep.plvt_ready ? 1 : 0;
   else if (n == "ip_iv_rows") *value = c->range.Rv;  // (the last range plan's interval-built rows)
   else if (n == "ip_range_rows") *value = c->range.Rr;  // (... and its range-built rows)
-  else if (n == "row_phases_active") *value = c->run.last.phase_used;  // (the last run's phases; 0: a plain run)
+  else if (n == "pod_post_rows" || n == "pod_scan_rows") {
+    // its sparse pod-peer rows, posting-built and scanned: launch C builds them on the fused front of PM builds only
+    const bool sparse = c->prepared && c->range.valid && c->route.fused && !c->route.ido && c->route.pod_sparse;
+    *value = !sparse ? 0 : n == "pod_post_rows" ? c->range.n_post : c->range.n_scan;
+  } else if (n == "row_phases_active") *value = c->run.last.phase_used;  // (the last run's phases; 0: a plain run)
   else if (n == "effects_batches") *value = c->effects.batches;  // (the last cyc_probe_target_effects call)
   else if (n == "effects_launches") *value = c->effects.launches;
   else if (n == "effects_scratch_bytes") *value = int64_t(c->effects.scratch);

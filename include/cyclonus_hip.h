@@ -608,7 +608,9 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  * run's phases: 2, or 0), "front_fused_active", "pl_wave_active" (needs cyc_probe_prepare),
  * "class_inplace_active" and "emit_interleave_active" (the routes in effect; they need a run),
  * "plvt_active", "ip_iv_rows" and "ip_range_rows" (the current range plan's
- * interval-built and range-built IP rows); "pod_words" reports the mode the prepared probe uses (0 or 1; needs
+ * interval-built and range-built IP rows), "pod_post_rows" and "pod_scan_rows" (its sparse pod-peer rows built
+ * from label postings and by scanning the pods; both 0 unless the route in effect builds sparse pod-peer rows:
+ * the fused front of a materialised-row build); "pod_words" reports the mode the prepared probe uses (0 or 1; needs
  * cyc_probe_prepare).  Of the last cyc_probe_target_effects call it reports "effects_batches" (class batches),
  * "effects_launches" (allow-row builds: one per batch and word window) and "effects_scratch_bytes" (device
  * bytes it held at its peak), and "effects_scratch_cap" reports the bytes its batch buffers may take (256 MB). */

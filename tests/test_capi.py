@@ -236,7 +236,7 @@ def test_option_table():
     fails("pl_wave_active: call cyc_probe_prepare first", e.get_option, "pl_wave_active")
     fails("class_inplace_active: run a probe first", e.get_option, "class_inplace_active")
     assert e.get_option("launch") == 1
-    for name in ("front_fused_active", "plvt_active", "ip_iv_rows", "ip_range_rows", "row_phases_active"):
+    for name in ("front_fused_active", "plvt_active", "ip_iv_rows", "ip_range_rows", "pod_post_rows", "pod_scan_rows", "row_phases_active"):
         assert e.get_option(name) == 0, name
     for name, (default, lo, hi) in OPTIONS.items():
         bounds = f"{name} must be in {lo}..{4 if name == 'row_phases' else hi}"

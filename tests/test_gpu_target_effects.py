@@ -243,7 +243,7 @@ def test_row_shards_add_up_and_blocked_ingress_count():
 
 # ---- a run's state is left alone
 ACTIVE = ("pod_words", "launch", "front_fused_active", "pl_wave_active", "class_inplace_active", "emit_interleave_active",
-          "plvt_active", "ip_iv_rows", "ip_range_rows", "row_phases_active")
+          "plvt_active", "ip_iv_rows", "ip_range_rows", "pod_post_rows", "pod_scan_rows", "row_phases_active")
 
 
 def test_runs_are_not_disturbed():
