@@ -60,10 +60,12 @@
 #include "dev_table.hpp"
 #include "dev_effects.hpp"
 
-// Host side: context, planner, enqueueing; the C ABI below
+// Host side: context, planner, enqueueing, the bodies of the effects and table calls; the C ABI below
 #include "ctx.hpp"
 #include "plan.hpp"
 #include "enqueue.hpp"
+#include "effects.hpp"
+#include "table.hpp"
 
 extern "C" {
 
@@ -390,333 +392,6 @@ int cyc_probe_run_host(cyc_ctx* c, uint64_t* h_in, uint64_t* h_eg, uint8_t* h_st
   return cyc_probe_run_host_rows(c, h_in, h_eg, h_status, CYC_ROWS_TARGET, lo, hi);
 }
 
-// ---------------------------------------------------------------- which target decides: per-target effect counts
-// The batch buffers' cap (dev_effects.hpp).  CYC_EFFECTS_SCRATCH_KB lowers or raises it for one process: a
-// development aid like CYC_TRACE_PREPARE, which lets a small problem go through several batches and windows.
-static uint64_t effects_scratch_cap() {
-  const char* e = getenv("CYC_EFFECTS_SCRATCH_KB");
-  if (e && *e) {
-    const long long kb = atoll(e);
-    if (kb > 0) return uint64_t(kb) << 10;
-  }
-  return EFF_SCRATCH_CAP;
-}
-
-extern "C++" {
-namespace {
-struct EffClass {  // target pods of the rows with one set of applying targets (ingress: and one descriptor per slot)
-  uint32_t list, row, pods;
-};
-struct EffBatch {
-  std::vector<uint32_t> tl;   // its targets, ascending
-  std::vector<uint32_t> cls;  // its classes
-  uint32_t WA = 0;            // words per window
-};
-std::string bytes_of(const void* p, size_t n) { return std::string(static_cast<const char*>(p), n); }
-}  // namespace
-
-// The call's body (cyc_probe_target_effects checked the arguments and zeroed the outputs; rows, T > 0).
-static int target_effects(cyc_ctx* c, int d, int64_t row_lo, int64_t row_hi, int64_t k_lo, int64_t k_hi, int64_t* effects,
-                          int64_t* applies) {
-  const Problem& pb = c->pb;
-  const Prepared& pr = c->prep;
-  hipStream_t st = c->stream;
-  const uint32_t P = pb.P, K = pb.K, W = pb.W, T = uint32_t(pb.tgt[d].size()), nk = uint32_t(k_hi - k_lo);
-  const uint32_t D = uint32_t(std::max<size_t>(pb.descs.size(), 1)), M = uint32_t(pb.pms.size());
-  const uint64_t cap = effects_scratch_cap();
-  uint64_t fixed = 0, peak = 0;  // scratch: tables alive for the whole call; with the batch buffers
-  auto held = [&](const DevBuf& b) { fixed += b.bytes; };
-  // CYC_TRACE_PREPARE=1: the call's host phases on stderr, and (synchronising after each) its kernels' times
-  PhaseClock clk("effects");
-  double k_ms[4] = {0, 0, 0, 0};  // allow rows, population counts, sole sweep, whatever else the stream held
-  auto kernel_done = [&](int which) {
-    if (!clk.on) return;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipStreamSynchronize(st));  // (the launches before it were timed by the previous call)
-    k_ms[which] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  };
-
-  // ---- the port table (k_portok), the call's own copy
-  DevBuf portok;
-  portok.alloc(std::max<uint64_t>(uint64_t(M) * D, 16));
-  held(portok);
-  const PortArgs pa{grid1(uint64_t(M) * D, 256), M, D, pr.pms.as<DPortM>(), pr.pents.as<DPortEntry>(), pr.descs.as<DDesc>(),
-                    portok.as<uint8_t>()};
-  if (pa.nb) k_portok<<<pa.nb, 256, 0, st>>>(pa);
-  HIPCHK(hipGetLastError());
-
-  EffTables x{};
-  x.P = P, x.K = K, x.W = W, x.D = D;
-  x.pod_ns = pr.pod_ns.as<uint32_t>(), x.pod_ls = pr.pod_ls.as<uint32_t>(), x.pod_nsls = pr.pod_nsls.as<uint32_t>();
-  x.pod_ip = pr.pod_ip.as<DIP>();
-  x.sel_off = pr.sel_off.as<uint32_t>(), x.req_vals = pr.req_vals.as<uint32_t>(), x.reqs = pr.reqs.as<DReq>();
-  x.ls_off = pr.ls_off.as<uint32_t>(), x.ls_key = pr.ls_key.as<uint32_t>(), x.ls_val = pr.ls_val.as<uint32_t>();
-  x.peers = pr.peers.as<DPeer>(), x.ipbs = pr.ipbs.as<DIPBlock>(), x.cidrs = pr.cidrs.as<DCidr>();
-  x.ipb_ex = pr.ipb_ex.as<uint32_t>();
-  x.tgt = pr.dir[d].tgt.as<DTarget>(), x.tns_lo = pr.dir[d].tns_lo.as<uint32_t>(), x.tns_hi = pr.dir[d].tns_hi.as<uint32_t>();
-  x.slot_desc = pr.slot_desc.as<int32_t>(), x.slot_status = pr.slot_status.as<uint8_t>();
-  x.portok = portok.as<uint8_t>();
-
-  // ---- TargetsApplyingToPod once per distinct (namespace, label set) of the rows' pods
-  const uint32_t rows = uint32_t(row_hi - row_lo);
-  std::vector<uint32_t> id_ns, id_ls, id_pods, pod_id(rows);
-  {
-    std::unordered_map<uint64_t, uint32_t> id_of;
-    for (uint32_t r = 0; r < rows; r++) {
-      const uint32_t q = uint32_t(row_lo) + r;
-      auto it = id_of.emplace(uint64_t(pb.pod_ns[q]) << 32 | pb.pod_ls[q], uint32_t(id_ns.size()));
-      if (it.second) id_ns.push_back(pb.pod_ns[q]), id_ls.push_back(pb.pod_ls[q]), id_pods.push_back(0);
-      pod_id[r] = it.first->second;
-      id_pods[pod_id[r]]++;
-    }
-  }
-  const uint32_t n_id = uint32_t(id_ns.size());
-  std::vector<uint32_t> cnt(n_id), off(n_id + 1, 0), list;
-  {
-    DevBuf d_ns, d_ls, d_cnt, d_off, d_list;
-    upload(d_ns, id_ns);
-    upload(d_ls, id_ls);
-    d_cnt.alloc(uint64_t(n_id) * 4);
-    EffMemberArgs ma{};
-    ma.x = x, ma.n = n_id, ma.id_ns = d_ns.as<uint32_t>(), ma.id_ls = d_ls.as<uint32_t>(), ma.cnt = d_cnt.as<uint32_t>();
-    k_eff_member<false><<<grid1(uint64_t(n_id) * 64, 256), 256, 0, st>>>(ma);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, uint64_t(n_id) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    uint64_t tot = 0;
-    for (uint32_t i = 0; i < n_id; i++) {
-      off[i] = uint32_t(tot);
-      tot += cnt[i];
-      if (tot > 0xFFFFFFFFull) throw Panic{CYC_ERR_OOM, "target effects: the rows' applying-target lists exceed 2^32 entries"};
-    }
-    off[n_id] = uint32_t(tot);
-    list.resize(tot);
-    if (tot) {
-      upload(d_off, off);
-      d_list.alloc(tot * 4);
-      ma.off = d_off.as<uint32_t>(), ma.list = d_list.as<uint32_t>();
-      k_eff_member<true><<<grid1(uint64_t(n_id) * 64, 256), 256, 0, st>>>(ma);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(list.data(), d_list.p, tot * 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-    peak = fixed + d_ns.bytes + d_ls.bytes + d_cnt.bytes + d_off.bytes + d_list.bytes;
-  }
-  clk.lap("membership");
-  if (applies)
-    for (uint32_t i = 0; i < n_id; i++)
-      for (uint32_t e = off[i]; e < off[i + 1]; e++) applies[list[e]] += id_pods[i];
-  c->effects.scratch = peak;
-  if (!nk) return (int)CYC_OK;
-
-  // ---- classes: (applying-target list, ingress: the slots' VALID descriptors) -> pods of the rows
-  std::vector<uint32_t> lid_of(n_id), l_off, l_len;  // distinct lists: a representative's span in `list`
-  {
-    std::unordered_map<std::string, uint32_t> seen;
-    for (uint32_t i = 0; i < n_id; i++) {
-      auto it = seen.emplace(bytes_of(list.data() + off[i], size_t(cnt[i]) * 4), uint32_t(l_off.size()));
-      if (it.second) l_off.push_back(off[i]), l_len.push_back(cnt[i]);
-      lid_of[i] = it.first->second;
-    }
-  }
-  std::vector<int32_t> row_desc;  // [distinct rows][nk]: the slot's descriptor when its job is VALID, else -1
-  std::vector<EffClass> cls;
-  {
-    std::unordered_map<std::string, uint32_t> seen_row;
-    std::unordered_map<uint64_t, uint32_t> seen_cls;
-    std::vector<int32_t> rd(nk);
-    for (uint32_t r = 0; r < rows; r++) {
-      const uint32_t q = uint32_t(row_lo) + r, lid = lid_of[pod_id[r]];
-      if (!l_len[lid]) continue;  // no target applies: no effect to count
-      uint32_t rid = 0;
-      if (d == 0) {
-        for (uint32_t kk = 0; kk < nk; kk++) {
-          const size_t at = size_t(q) * K + size_t(k_lo) + kk;
-          rd[kk] = pb.slot_status[at] == CYC_JOB_VALID ? pb.slot_desc[at] : -1;
-        }
-        auto it = seen_row.emplace(bytes_of(rd.data(), size_t(nk) * 4), uint32_t(seen_row.size()));
-        if (it.second) row_desc.insert(row_desc.end(), rd.begin(), rd.end());
-        rid = it.first->second;
-      }
-      auto it = seen_cls.emplace(uint64_t(lid) << 32 | rid, uint32_t(cls.size()));
-      if (it.second) cls.push_back(EffClass{lid, rid, 0});
-      cls[it.first->second].pods++;
-    }
-  }
-  if (cls.empty()) return (int)CYC_OK;
-  // classes of one namespace side by side (their targets are one run of the primary-key order)
-  std::sort(cls.begin(), cls.end(), [&](const EffClass& a, const EffClass& b) {
-    const uint32_t fa = list[l_off[a.list]], fb = list[l_off[b.list]];
-    return fa != fb ? fa < fb : a.list != b.list ? a.list < b.list : a.row < b.row;
-  });
-
-  clk.lap("classes");
-  // ---- egress: the VALID pods of every (slot, descriptor) as bit rows, and their number per slot
-  std::vector<int64_t> n_valid(nk, 0);
-  DevBuf V;
-  if (d == 1) {
-    for (uint32_t q = 0; q < P; q++)
-      for (uint32_t kk = 0; kk < nk; kk++) n_valid[kk] += pb.slot_status[size_t(q) * K + size_t(k_lo) + kk] == CYC_JOB_VALID;
-    V.alloc(std::max<uint64_t>(uint64_t(nk) * D * W * 8, 16));
-    held(V);
-    EffValidArgs va{x, uint32_t(k_lo), nk, V.as<uint64_t>()};
-    k_eff_valid<<<grid1(uint64_t(nk) * W * 64, 256), 256, 0, st>>>(va);
-    HIPCHK(hipGetLastError());
-  }
-
-  // ---- batches: classes in order while the union of their targets' rows fits the cap; a batch of one class
-  // that does not fit whole is built a window of words at a time
-  const uint32_t X = d == 0 ? D : nk;  // population counts per target
-  const uint64_t per_t = uint64_t(X + nk) * 8, per_tw = uint64_t(D) * 8;  // bytes per target; per target and word
-  std::vector<EffBatch> batches;
-  {
-    std::vector<uint32_t> stamp(T, 0);
-    for (uint32_t ci = 0; ci < cls.size(); ci++) {
-      const uint32_t* L = list.data() + l_off[cls[ci].list];
-      const uint32_t n = l_len[cls[ci].list];
-      for (int attempt = 0; attempt < 2; attempt++) {
-        if (batches.empty() || attempt) batches.emplace_back();
-        EffBatch& b = batches.back();
-        const uint32_t id = uint32_t(batches.size());
-        uint32_t fresh = 0;
-        for (uint32_t e = 0; e < n; e++) fresh += stamp[L[e]] != id;
-        const uint64_t U = b.tl.size() + fresh;
-        if (!b.cls.empty() && U * (per_t + per_tw * W) > cap) continue;  // (a new batch takes it)
-        if (U * (per_t + per_tw) > cap)
-          throw Panic{CYC_ERR_OOM, "target effects: " + std::to_string(U) + " targets apply to one pod; their rows of one word exceed the scratch cap"};
-        for (uint32_t e = 0; e < n; e++)
-          if (stamp[L[e]] != id) stamp[L[e]] = id, b.tl.push_back(L[e]);
-        b.cls.push_back(ci);
-        break;
-      }
-    }
-    for (EffBatch& b : batches) {
-      std::sort(b.tl.begin(), b.tl.end());
-      const uint64_t U = b.tl.size();
-      b.WA = uint32_t(std::min<uint64_t>(W, (cap - U * per_t) / (U * per_tw)));
-    }
-  }
-
-  // ---- the batch buffers, sized for the largest batch
-  uint64_t max_a = 0, max_u = 0, max_ct = 0, max_c = 0;
-  for (const EffBatch& b : batches) {
-    max_a = std::max<uint64_t>(max_a, uint64_t(b.tl.size()) * D * b.WA);
-    max_u = std::max<uint64_t>(max_u, b.tl.size());
-    uint64_t ct = 0;
-    for (uint32_t ci : b.cls) ct += l_len[cls[ci].list];
-    max_ct = std::max(max_ct, ct);
-    max_c = std::max<uint64_t>(max_c, b.cls.size());
-  }
-  DevBuf d_a, d_pop, d_sole, d_tl, d_coff, d_ct, d_cn, d_cd;
-  d_a.alloc(max_a * 8);
-  d_pop.alloc(max_u * X * 8);
-  d_sole.alloc(max_u * nk * 8);
-  d_tl.alloc(max_u * 4);
-  d_coff.alloc((max_c + 1) * 4);
-  d_ct.alloc(max_ct * 4);
-  d_cn.alloc(max_c * 4);
-  d_cd.alloc(std::max<uint64_t>(max_c * nk * 4, 16));
-  peak = std::max(peak, fixed + d_a.bytes + d_pop.bytes + d_sole.bytes + d_tl.bytes + d_coff.bytes + d_ct.bytes + d_cn.bytes + d_cd.bytes);
-  c->effects.scratch = peak;
-
-  // effects[.][1] and [.][3] hold the applicable VALID cells (of all classes; of one-target classes) until
-  // the end; allow1 the ALLOWING cells of one-target classes
-  std::vector<int64_t> allow1(size_t(T) * nk, 0);
-  std::vector<uint32_t> loc(T, 0), coff, ct, cn;
-  std::vector<int32_t> cd;
-  std::vector<unsigned long long> pop, sole;
-  for (const EffBatch& b : batches) {
-    const uint32_t U = uint32_t(b.tl.size());
-    for (uint32_t u = 0; u < U; u++) loc[b.tl[u]] = u;
-    // the classes of two or more targets, for the sole sweep
-    coff.assign(1, 0), ct.clear(), cn.clear(), cd.clear();
-    for (uint32_t ci : b.cls) {
-      const EffClass& k = cls[ci];
-      const uint32_t* L = list.data() + l_off[k.list];
-      const uint32_t n = l_len[k.list];
-      for (uint32_t kk = 0; kk < nk; kk++) {  // the applicable VALID cells (window-independent)
-        const int64_t cells = d == 0 ? (row_desc[size_t(k.row) * nk + kk] >= 0 ? int64_t(P) : 0) : n_valid[kk];
-        for (uint32_t e = 0; e < n; e++) {
-          int64_t* o = effects + (size_t(L[e]) * nk + kk) * 4;
-          o[CYC_EFFECT_DENYING] += cells * k.pods;
-          if (n == 1) o[CYC_EFFECT_SOLE_DENYING] += cells * k.pods;
-        }
-      }
-      if (n < 2) continue;
-      for (uint32_t e = 0; e < n; e++) ct.push_back(loc[L[e]]);
-      coff.push_back(uint32_t(ct.size()));
-      cn.push_back(k.pods);
-      if (d == 0) cd.insert(cd.end(), row_desc.begin() + size_t(k.row) * nk, row_desc.begin() + size_t(k.row + 1) * nk);
-    }
-    const uint32_t NC = uint32_t(cn.size());
-    HIPCHK(hipMemcpyAsync(d_tl.p, b.tl.data(), size_t(U) * 4, hipMemcpyHostToDevice, st));
-    if (NC) {
-      HIPCHK(hipMemcpyAsync(d_coff.p, coff.data(), coff.size() * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_ct.p, ct.data(), ct.size() * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_cn.p, cn.data(), cn.size() * 4, hipMemcpyHostToDevice, st));
-      if (d == 0) HIPCHK(hipMemcpyAsync(d_cd.p, cd.data(), cd.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    pop.resize(size_t(U) * X);
-    sole.resize(size_t(U) * nk);
-    for (uint32_t w0 = 0; w0 < W; w0 += b.WA) {
-      const uint32_t WA = std::min(b.WA, W - w0);
-      EffRowArgs ra{x, U, w0, WA, d_tl.as<uint32_t>(), d_a.as<uint64_t>()};
-      kernel_done(3);  // (uploads, k_eff_valid)
-      k_eff_rows<<<grid1(uint64_t(U) * WA * 64, 256), 256, 0, st>>>(ra);
-      HIPCHK(hipGetLastError());
-      kernel_done(0);
-      EffPopArgs pa2{D, W, w0, WA, X, d_a.as<uint64_t>(), V.as<uint64_t>(), d_pop.as<unsigned long long>()};
-      if (d == 0) k_eff_pop<false><<<unsigned(uint64_t(U) * X), 256, 0, st>>>(pa2);
-      else k_eff_pop<true><<<unsigned(uint64_t(U) * X), 256, 0, st>>>(pa2);
-      HIPCHK(hipGetLastError());
-      kernel_done(1);
-      if (NC) {
-        HIPCHK(hipMemsetAsync(d_sole.p, 0, size_t(U) * nk * 8, st));
-        EffSoleArgs sa{D, W, w0, WA, nk, NC, d_a.as<uint64_t>(), V.as<uint64_t>(), d_coff.as<uint32_t>(), d_ct.as<uint32_t>(),
-                       d_cn.as<uint32_t>(), d_cd.as<int32_t>(), d_sole.as<unsigned long long>()};
-        const unsigned nb = grid1(uint64_t(NC) * nk * ((WA + 255) / 256), 1);
-        if (d == 0) k_eff_sole<false><<<nb, 256, 0, st>>>(sa);
-        else k_eff_sole<true><<<nb, 256, 0, st>>>(sa);
-        HIPCHK(hipGetLastError());
-        kernel_done(2);
-        HIPCHK(hipMemcpyAsync(sole.data(), d_sole.p, sole.size() * 8, hipMemcpyDeviceToHost, st));
-      }
-      HIPCHK(hipMemcpyAsync(pop.data(), d_pop.p, pop.size() * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      c->effects.launches++;
-      for (uint32_t ci : b.cls) {
-        const EffClass& k = cls[ci];
-        const uint32_t* L = list.data() + l_off[k.list];
-        const uint32_t n = l_len[k.list];
-        for (uint32_t kk = 0; kk < nk; kk++) {
-          const int32_t j = d == 0 ? row_desc[size_t(k.row) * nk + kk] : int32_t(kk);
-          if (j < 0) continue;
-          for (uint32_t e = 0; e < n; e++) {
-            const int64_t v = int64_t(pop[size_t(loc[L[e]]) * X + uint32_t(j)]) * k.pods;
-            effects[(size_t(L[e]) * nk + kk) * 4 + CYC_EFFECT_ALLOWING] += v;
-            if (n == 1) allow1[size_t(L[e]) * nk + kk] += v;
-          }
-        }
-      }
-      if (NC)
-        for (uint32_t u = 0; u < U; u++)
-          for (uint32_t kk = 0; kk < nk; kk++)
-            effects[(size_t(b.tl[u]) * nk + kk) * 4 + CYC_EFFECT_SOLE_ALLOWING] += int64_t(sole[size_t(u) * nk + kk]);
-    }
-    c->effects.batches++;
-  }
-  clk.lap("batches");
-  if (clk.on)
-    fprintf(stderr, "[cyc effects] %lld batches, %lld row builds, %zu classes: k_eff_rows %.2f ms, k_eff_pop %.2f ms, k_eff_sole %.2f ms, other %.2f ms\n",
-            (long long)c->effects.batches, (long long)c->effects.launches, cls.size(), k_ms[0], k_ms[1], k_ms[2], k_ms[3]);
-  for (size_t i = 0; i < size_t(T) * nk; i++) {
-    effects[i * 4 + CYC_EFFECT_DENYING] -= effects[i * 4 + CYC_EFFECT_ALLOWING];
-    effects[i * 4 + CYC_EFFECT_SOLE_DENYING] -= allow1[i];
-  }
-  return (int)CYC_OK;
-}
-}  // extern "C++"
-
 int cyc_probe_target_effects(cyc_ctx* c, int direction, int64_t row_lo, int64_t row_hi, int64_t k_lo, int64_t k_hi, int64_t* effects,
                              int64_t* applies) {
   if (!c) return CYC_ERR_ARG;
@@ -740,83 +415,12 @@ int cyc_probe_target_effects(cyc_ctx* c, int direction, int64_t row_lo, int64_t 
   });
 }
 
-// ---------------------------------------------------------------- device-resident tables
-struct cyc_table {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  uint32_t P = 0, K = 0, W = 0;
-  int64_t row_lo = 0, row_hi = 0;
-  int partition = CYC_ROWS_TARGET;  // CYC_ROWS_SOURCE: rows are sources; ingress rows cover words [w0, w0 + wa)
-  uint32_t w0 = 0, wa = 0;
-  const uint64_t *in = nullptr, *eg = nullptr;
-  const uint8_t* status = nullptr;
-  DevBuf own_in, own_eg, own_st;  // cyc_table_run: the table owns its planes
-};
-
-// Plane shapes of rows [lo, hi) under a partition: ingress rows, words per ingress row slot, egress
-// rows, words per egress row slot, first word of the ingress window.
-static bool rows_layout(const cyc_ctx* c, int part, int64_t lo, int64_t hi, int64_t v[5], std::string& why) {
-  const int64_t P = c->pb.P, W = c->pb.W;
-  // a context prepared for batched blocks has per-block slabs, not row planes (cyc_probe_run_blocks)
-  if (!c->pb.blocks.empty()) return why = "context prepared for blocks: use cyc_probe_run_blocks", false;
-  if (part != CYC_ROWS_TARGET && part != CYC_ROWS_SOURCE) return why = "unknown partition", false;
-  if (lo < 0 || hi > P || lo > hi) return why = "row range out of bounds", false;
-  if (part == CYC_ROWS_SOURCE && (lo % 64 || (hi % 64 && hi != P)))
-    return why = "source rows: row_lo must be a multiple of 64, row_hi too unless it is the pod count", false;
-  const bool src = part == CYC_ROWS_SOURCE;
-  const int64_t wa = src ? (hi > lo ? (hi + 63) / 64 - lo / 64 : 0) : W;
-  v[0] = src ? P : hi - lo;
-  v[1] = wa;
-  v[2] = hi - lo;
-  v[3] = W;
-  v[4] = src ? lo / 64 : 0;
-  return true;
-}
-
-static int table_new(cyc_ctx* c, int part, int64_t lo, int64_t hi, cyc_table** out) {
-  int64_t v[5];
-  std::string why;
-  if (!rows_layout(c, part, lo, hi, v, why)) return fail(c, CYC_ERR_ARG, why);
-  auto* t = new cyc_table();
-  t->device = c->device;
-  t->P = c->pb.P;
-  t->K = c->pb.K;
-  t->W = c->pb.W;
-  t->row_lo = lo;
-  t->row_hi = hi;
-  t->partition = part;
-  t->w0 = uint32_t(v[4]);
-  t->wa = uint32_t(v[1]);
-  *out = t;
-  return (int)CYC_OK;
-}
-
+// ---------------------------------------------------------------- device-resident tables (table.hpp)
 int cyc_table_run_rows(cyc_ctx* c, int part, int64_t lo, int64_t hi, cyc_table** out) {
   if (!c || !out) return CYC_ERR_ARG;
   *out = nullptr;
   if (!c->prepared) return fail(c, CYC_ERR_ARG, "cyc_probe_prepare first");
-  return guarded(c, [&]() -> int {
-    DeviceGuard dg(c->device);
-    cyc_table* t = nullptr;
-    int rc = table_new(c, part, lo, hi, &t);
-    if (rc != CYC_OK) return rc;
-    std::unique_ptr<cyc_table> hold(t);
-    const uint64_t words_in = uint64_t(part == CYC_ROWS_SOURCE ? c->pb.P : hi - lo) * c->pb.K * t->wa;
-    const uint64_t words_eg = uint64_t(hi - lo) * c->pb.K * c->pb.W;
-    t->own_in.alloc(std::max<uint64_t>(words_in * 8, 16));
-    t->own_eg.alloc(std::max<uint64_t>(words_eg * 8, 16));
-    t->own_st.alloc(std::max<uint64_t>(uint64_t(c->pb.P) * c->pb.K, 16));
-    t->in = t->own_in.as<uint64_t>();
-    t->eg = t->own_eg.as<uint64_t>();
-    t->status = t->own_st.as<uint8_t>();
-    rc = run_pipeline(c, c->stream, t->own_in.as<uint64_t>(), t->own_eg.as<uint64_t>(), t->own_st.as<uint8_t>(), lo, hi,
-                      false, part == CYC_ROWS_SOURCE);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (rc != CYC_OK) return rc;
-    *out = hold.release();
-    return (int)CYC_OK;
-  });
+  return table_run(c, part, lo, hi, out);
 }
 
 int cyc_table_run(cyc_ctx* c, int64_t lo, int64_t hi, cyc_table** out) { return cyc_table_run_rows(c, CYC_ROWS_TARGET, lo, hi, out); }
@@ -831,9 +435,7 @@ int cyc_table_wrap_rows(cyc_ctx* c, const uint64_t* d_in, const uint64_t* d_eg, 
   cyc_table* t = nullptr;
   int rc = table_new(c, part, lo, hi, &t);
   if (rc != CYC_OK) return rc;
-  t->in = d_in;
-  t->eg = d_eg;
-  t->status = d_status;
+  t->in = d_in, t->eg = d_eg, t->status = d_status;
   *out = t;
   return (int)CYC_OK;
 }
@@ -864,761 +466,50 @@ int cyc_table_shape(const cyc_table* t, int64_t* out, int n) {
 
 int cyc_table_cells(cyc_table* t, int64_t s_lo, int64_t s_hi, int64_t d_lo, int64_t d_hi, int64_t k_lo, int64_t k_hi,
                     uint8_t* ingress, uint8_t* egress, uint8_t* combined) {
-  if (!t) return CYC_ERR_ARG;
-  auto bad = [&](const char* m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  if (s_lo < 0 || s_hi > int64_t(t->P) || s_lo > s_hi || d_lo < 0 || d_hi > int64_t(t->P) || d_lo > d_hi || k_lo < 0 ||
-      k_hi > int64_t(t->K) || k_lo > k_hi)
-    return bad("cell range out of bounds");
-  // ingress rows are keyed by destination, egress rows by source (include/cyclonus_hip.h); a
-  // source-row table holds both directions of its sources' cells
-  const bool src = t->partition == CYC_ROWS_SOURCE;
-  const bool need_d = !src && (ingress || combined), need_s = egress || combined || (src && ingress);
-  if (s_hi > s_lo && d_hi > d_lo && k_hi > k_lo) {
-    if (need_d && (d_lo < t->row_lo || d_hi > t->row_hi)) return bad("ingress cells need destinations inside the table's rows");
-    if (need_s && (s_lo < t->row_lo || s_hi > t->row_hi))
-      return bad(src ? "cells of a source-row table need sources inside its rows" : "egress cells need sources inside the table's rows");
-  }
-  const uint64_t n = uint64_t(s_hi - s_lo) * uint64_t(d_hi - d_lo) * uint64_t(k_hi - k_lo);
-  if (!n) return (int)CYC_OK;
-  try {
-    DeviceGuard dg(t->device);
-    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    DevBuf o[3];
-    uint8_t* host[3] = {ingress, egress, combined};
-    for (int x = 0; x < 3; x++)
-      if (host[x]) o[x].alloc(n);
-    CellArgs a{};
-    a.K = t->K;
-    a.W = t->W;
-    a.row_lo = uint32_t(t->row_lo);
-    a.row_hi = uint32_t(t->row_hi);
-    a.src = src ? 1u : 0u;
-    a.w0 = t->w0;
-    a.WA = t->wa;
-    a.in = t->in;
-    a.eg = t->eg;
-    a.status = t->status;
-    a.s_lo = uint32_t(s_lo);
-    a.d_lo = uint32_t(d_lo);
-    a.k_lo = uint32_t(k_lo);
-    a.nd = uint32_t(d_hi - d_lo);
-    a.nk = uint32_t(k_hi - k_lo);
-    a.n = n;
-    a.o_in = o[0].as<uint8_t>();
-    a.o_eg = o[1].as<uint8_t>();
-    a.o_comb = o[2].as<uint8_t>();
-    k_table_cells<<<grid1(n, 256), 256, 0, t->stream>>>(a);
-    HIPCHK(hipGetLastError());
-    for (int x = 0; x < 3; x++)
-      if (host[x]) HIPCHK(hipMemcpyAsync(host[x], o[x].p, n, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-  } catch (HipErr& h) {
-    t->err = h.msg;
-    return (int)CYC_ERR_HIP;
-  } catch (std::bad_alloc&) {
-    t->err = "host allocation failed";
-    return (int)CYC_ERR_OOM;
-  }
-  return (int)CYC_OK;
-}
-
-// ---------------------------------------------------------------- whole-table counts and comparison
-// Failures of the table entry points land in cyc_table_error(t), as cyc_table_cells' do.
-static int table_guarded(cyc_table* t, const std::function<int()>& f) {
-  try {
-    return f();
-  } catch (HipErr& h) {
-    t->err = h.msg;
-    return (int)CYC_ERR_HIP;
-  } catch (std::bad_alloc&) {
-    t->err = "host allocation failed";
-    return (int)CYC_ERR_OOM;
-  }
-}
-
-static bool table_whole(const cyc_table* t) {
-  return t->partition == CYC_ROWS_SOURCE || (t->row_lo == 0 && t->row_hi == int64_t(t->P));
-}
-
-// The tile kernel's view of a whole target-row table (sources [0, P)) or of a source-row table.
-static TileArgs tile_args(const cyc_table* t, int64_t k_lo, int64_t k_hi) {
-  TileArgs a{};
-  a.P = t->P, a.K = t->K, a.W = t->W;
-  a.WA = t->wa, a.w0 = t->w0;
-  a.s_lo = uint32_t(t->row_lo), a.s_hi = uint32_t(t->row_hi);
-  a.k_lo = uint32_t(k_lo), a.nk = uint32_t(k_hi - k_lo);
-  a.a = TablePlanes{t->in, t->eg, t->status};
-  return a;
-}
-
-static dim3 tile_grid(const cyc_table* t, uint32_t source_words = TT_WORDS) {
-  return dim3((t->W + TT_WORDS - 1) / TT_WORDS, (t->wa + source_words - 1) / source_words);
+  return t ? table_cells(t, s_lo, s_hi, d_lo, d_hi, k_lo, k_hi, ingress, egress, combined) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_counts(cyc_table* t, int64_t k_lo, int64_t k_hi, int64_t* ingress, int64_t* egress, int64_t* combined,
                      int64_t* no_job) {
-  if (!t) return CYC_ERR_ARG;
-  auto bad = [&](const char* m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
-  if (!ingress && !egress && !combined && !no_job) return bad("no output requested");
-  const bool whole = table_whole(t);
-  // a partial target-row table holds the ingress rows of its destinations and the egress rows of its
-  // sources: no cell has both
-  if (!whole && (combined || no_job)) return bad("ingress cells need destinations inside the table's rows");
-  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
-  for (int64_t i = 0; i < nk * 6; i++) {
-    if (ingress) ingress[i] = 0;
-    if (egress) egress[i] = 0;
-    if (combined) combined[i] = 0;
-  }
-  if (no_job) *no_job = 0;
-  if (!nk || !P) return (int)CYC_OK;
-  return table_guarded(t, [&]() -> int {
-    DeviceGuard dg(t->device);
-    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    // allowed cells per (row, slot): whole tables [nk][3][P] by destination (Ingress, Egress, Combined);
-    // partial ones [rows][nk][2] (Ingress of destination row r, Egress of source row r)
-    const int per = whole ? 3 : 2;
-    const uint64_t n_cnt = uint64_t(whole ? P : rows) * nk * per;
-    std::vector<unsigned long long> cnt(n_cnt, 0);
-    std::vector<uint8_t> st(size_t(P) * K);
-    DevBuf d_cnt, d_valid;
-    if (n_cnt) {
-      d_cnt.alloc(n_cnt * 8);
-      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
-    }
-    if (whole && rows) {
-      TileArgs a = tile_args(t, k_lo, k_hi);
-      a.cnt = d_cnt.as<unsigned long long>();
-      k_table_tiles<false><<<tile_grid(t), 1024, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-    } else if (rows) {
-      RowCountArgs a{};
-      a.P = t->P, a.K = t->K, a.W = t->W, a.row_lo = uint32_t(t->row_lo), a.rows = uint32_t(rows);
-      a.k_lo = uint32_t(k_lo), a.nk = uint32_t(nk);
-      a.t = TablePlanes{t->in, t->eg, t->status};
-      d_valid.alloc(uint64_t(nk) * t->W * 8);
-      a.valid = d_valid.as<uint64_t>();
-      a.cnt = d_cnt.as<unsigned long long>();
-      k_table_valid_words<<<grid1(uint64_t(nk) * t->W, 256), 256, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-      k_table_row_counts<<<unsigned((uint64_t(rows) * nk + 3) / 4), 256, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-    }
-    if (n_cnt) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipMemcpyAsync(st.data(), t->status, st.size(), hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    // the status-only terms (jobrunner.go:36-55): a BadPortProtocol / BadNamedPort job is one code for
-    // every source of the destination, Egress unknown; a slot without a job is CYC_CONN_NO_JOB
-    const int64_t n_src = whole ? rows : P;  // sources of an ingress row's cells
-    for (int64_t kk = 0; kk < nk; kk++) {
-      int64_t* oi = ingress ? ingress + kk * 6 : nullptr;
-      int64_t* oe = egress ? egress + kk * 6 : nullptr;
-      int64_t* oc = combined ? combined + kk * 6 : nullptr;
-      // ingress (and combined) over the destinations the table answers; egress over every destination
-      for (int64_t d = 0; d < P; d++) {
-        const uint8_t s = st[size_t(d * K + k_lo + kk)];
-        const bool in_rows = whole || (d >= t->row_lo && d < t->row_hi);
-        const int inv = s == CYC_JOB_BAD_PORT_PROTOCOL ? CYC_CONN_INVALID_PORT_PROTOCOL : CYC_CONN_INVALID_NAMED_PORT;
-        if (s == CYC_JOB_VALID) {
-          if (whole) {
-            const unsigned long long* c = &cnt[size_t(kk * 3 * P + d)];
-            if (oi) oi[CYC_CONN_ALLOWED] += int64_t(c[0]), oi[CYC_CONN_BLOCKED] += rows - int64_t(c[0]);
-            if (oe) oe[CYC_CONN_ALLOWED] += int64_t(c[P]), oe[CYC_CONN_BLOCKED] += rows - int64_t(c[P]);
-            if (oc) oc[CYC_CONN_ALLOWED] += int64_t(c[2 * P]), oc[CYC_CONN_BLOCKED] += rows - int64_t(c[2 * P]);
-          } else {
-            if (oi && in_rows) {
-              const int64_t c = int64_t(cnt[size_t(((d - t->row_lo) * nk + kk) * 2)]);
-              oi[CYC_CONN_ALLOWED] += c, oi[CYC_CONN_BLOCKED] += n_src - c;
-            }
-            if (oe) oe[CYC_CONN_BLOCKED] += rows;  // (the allowed ones move over below)
-          }
-        } else if (s == CYC_JOB_NONE) {
-          if (no_job) *no_job += rows;
-        } else {
-          if (oi && in_rows) oi[inv] += n_src;
-          if (oc) oc[inv] += rows;
-          if (oe) oe[CYC_CONN_UNKNOWN] += rows;
-        }
-      }
-      if (!whole && oe)
-        for (int64_t r = 0; r < rows; r++) {
-          const int64_t c = int64_t(cnt[size_t((r * nk + kk) * 2 + 1)]);
-          oe[CYC_CONN_ALLOWED] += c, oe[CYC_CONN_BLOCKED] -= c;
-        }
-    }
-    return (int)CYC_OK;
-  });
+  return t ? table_counts(t, k_lo, k_hi, ingress, egress, combined, no_job) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_pod_counts(cyc_table* t, int view, int64_t k_lo, int64_t k_hi, int64_t* by_src, int64_t* by_dst) {
-  if (!t) return CYC_ERR_ARG;
-  auto bad = [&](const char* m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  if (view != CYC_VIEW_INGRESS && view != CYC_VIEW_EGRESS && view != CYC_VIEW_COMBINED) return bad("unknown view");
-  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
-  if (!by_src && !by_dst) return bad("no output requested");
-  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
-  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
-  if (!nk || !P) return (int)CYC_OK;
-  return table_guarded(t, [&]() -> int {
-    DeviceGuard dg(t->device);
-    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    // allowed cells per (slot, destination) of the three views (cyc_table_counts), and with by_src per (slot,
-    // source) of `view`
-    const int64_t src_stride = int64_t(t->wa) * 64;  // (TileArgs::src_cnt: source-minor)
-    const uint64_t n_cnt = uint64_t(nk) * 3 * P, n_src = by_src ? uint64_t(nk) * src_stride : 0;
-    std::vector<unsigned long long> cnt(n_cnt, 0), src(n_src, 0);
-    std::vector<uint8_t> st(size_t(P) * K);
-    DevBuf d_cnt;
-    if (rows) {
-      d_cnt.alloc((n_cnt + n_src) * 8);
-      HIPCHK(hipMemsetAsync(d_cnt.p, 0, (n_cnt + n_src) * 8, t->stream));
-      TileArgs a = tile_args(t, k_lo, k_hi);
-      a.cnt = d_cnt.as<unsigned long long>();
-      a.src_cnt = a.cnt + n_cnt;
-      a.view = uint32_t(view);
-      if (by_src) k_table_tiles<false, true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
-      else k_table_tiles<false><<<tile_grid(t), 1024, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(cnt.data(), a.cnt, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
-      if (n_src) HIPCHK(hipMemcpyAsync(src.data(), a.src_cnt, n_src * 8, hipMemcpyDeviceToHost, t->stream));
-    }
-    HIPCHK(hipMemcpyAsync(st.data(), t->status, st.size(), hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    // the status-only terms, as cyc_table_counts': the code of a destination's slot that is not VALID holds for
-    // every source, so a source's row has as many cells of it as there are such destinations
-    const int inv_np = view == CYC_VIEW_EGRESS ? CYC_CONN_UNKNOWN : CYC_CONN_INVALID_NAMED_PORT;
-    const int inv_pp = view == CYC_VIEW_EGRESS ? CYC_CONN_UNKNOWN : CYC_CONN_INVALID_PORT_PROTOCOL;
-    for (int64_t kk = 0; kk < nk; kk++) {
-      int64_t n_of[4] = {0, 0, 0, 0};  // destinations per cyc_job_status
-      for (int64_t d = 0; d < P; d++) {
-        const uint8_t s = st[size_t(d * K + k_lo + kk)];
-        n_of[s <= CYC_JOB_BAD_PORT_PROTOCOL ? s : CYC_JOB_BAD_NAMED_PORT]++;  // (any other value: as cyc_table_counts)
-        if (!by_dst) continue;
-        int64_t* o = by_dst + (d * nk + kk) * CYC_POD_CODES;
-        for (int c = 0; c < CYC_POD_CODES; c++) o[c] = 0;
-        if (s == CYC_JOB_VALID) {
-          const int64_t a = int64_t(cnt[size_t((kk * 3 + view) * P + d)]);
-          o[CYC_CONN_ALLOWED] = a, o[CYC_CONN_BLOCKED] = rows - a;
-        } else {
-          o[s == CYC_JOB_NONE ? 6 : s == CYC_JOB_BAD_PORT_PROTOCOL ? inv_pp : inv_np] = rows;
-        }
-      }
-      for (int64_t i = 0; by_src && i < rows; i++) {
-        int64_t* o = by_src + (i * nk + kk) * CYC_POD_CODES;
-        for (int c = 0; c < CYC_POD_CODES; c++) o[c] = 0;
-        const int64_t a = int64_t(src[size_t(kk * src_stride + i)]);
-        o[CYC_CONN_ALLOWED] = a, o[CYC_CONN_BLOCKED] = n_of[CYC_JOB_VALID] - a;
-        o[inv_np] += n_of[CYC_JOB_BAD_NAMED_PORT], o[inv_pp] += n_of[CYC_JOB_BAD_PORT_PROTOCOL];
-        o[6] = n_of[CYC_JOB_NONE];
-      }
-    }
-    return (int)CYC_OK;
-  });
-}
-
-// What cyc_table_compare and cyc_table_pod_compare check alike; nullptr when the arguments are fine.
-static const char* compare_args_bad(const cyc_table* ta, const cyc_table* tb, int64_t k_lo, int64_t k_hi) {
-  if (!tb) return "null table";
-  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition ||
-      ta->row_lo != tb->row_lo || ta->row_hi != tb->row_hi)
-    return "cannot compare tables of different devices, shapes, partitions or rows";
-  if (k_lo < 0 || k_hi > int64_t(ta->K) || k_lo > k_hi) return "slot range out of bounds";
-  if (!table_whole(ta)) return "ingress cells need destinations inside the table's rows";
-  return nullptr;
-}
-
-// The compare pass over the tiles and what the host needs of it: the kernel's per-destination buffer (TileArgs::cnt),
-// with `src` its per-source buffer (TileArgs::src_cnt) too, and a's status plane.  Zeros where the table has no cell.
-struct CompareTiles {
-  std::vector<unsigned long long> cnt, src;
-  std::vector<uint8_t> sa;
-};
-static CompareTiles compare_tiles(cyc_table* t, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, uint64_t* d_diff,
-                                  bool src) {
-  const uint64_t nk = uint64_t(k_hi - k_lo), P = t->P, n_cnt = P * (nk + 2), n_src = src ? (nk + 1) * t->wa * 64 : 0;
-  CompareTiles r;
-  r.cnt.assign(n_cnt, 0), r.src.assign(n_src, 0), r.sa.assign(size_t(P) * t->K, 0);
-  if (!P || t->row_hi == t->row_lo) return r;
-  if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-  DevBuf d_cnt;
-  d_cnt.alloc((n_cnt + n_src) * 8);
-  HIPCHK(hipMemsetAsync(d_cnt.p, 0, (n_cnt + n_src) * 8, t->stream));
-  TileArgs a = tile_args(t, k_lo, k_hi);
-  a.b = TablePlanes{tb->in, tb->eg, tb->status};
-  a.ignore_loopback = ignore_loopback ? 1u : 0u;
-  a.cnt = d_cnt.as<unsigned long long>();
-  a.src_cnt = a.cnt + n_cnt;
-  a.diff = d_diff;
-  if (src) k_table_tiles<true, true><<<tile_grid(t, tile_source_words(true, true)), 1024, 0, t->stream>>>(a);
-  else k_table_tiles<true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(r.cnt.data(), a.cnt, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
-  if (n_src) HIPCHK(hipMemcpyAsync(r.src.data(), a.src_cnt, n_src * 8, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipMemcpyAsync(r.sa.data(), t->status, r.sa.size(), hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));  // (d_cnt is freed after it)
-  return r;
-}
-
-// per job (ValueCountsByProtocol :89-107, ResultsByProtocol :14-20,69-79): every cell whose job a holds, summed
-// (slot_counts) and per destination (dst_counts), each optional
-static void compare_jobs_by_dst(const cyc_table* t, const CompareTiles& r, int64_t k_lo, int64_t nk, int ignore_loopback,
-                                int64_t* slot_counts, int64_t* dst_counts) {
-  const int64_t P = t->P, K = t->K, rows = t->row_hi - t->row_lo;
-  for (int64_t i = 0; slot_counts && i < nk * 3; i++) slot_counts[i] = 0;
-  if (slot_counts || dst_counts)
-    for (int64_t d = 0; d < P; d++)
-      for (int64_t kk = 0; kk < nk; kk++) {
-        int64_t v[3] = {0, 0, 0};
-        if (r.sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE) {
-          v[2] = ignore_loopback && d >= t->row_lo && d < t->row_hi ? 1 : 0;
-          v[1] = int64_t(r.cnt[size_t(kk * P + d)]);
-          v[0] = rows - v[1] - v[2];
-        }
-        for (int x = 0; x < 3; x++) {
-          if (slot_counts) slot_counts[kk * 3 + x] += v[x];
-          if (dst_counts) dst_counts[(d * nk + kk) * 3 + x] = v[x];
-        }
-      }
+  return t ? table_pod_counts(t, view, k_lo, k_hi, by_src, by_dst) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t pair_counts[3],
                       int64_t* slot_counts, int64_t* dst_counts, uint64_t* d_diff) {
-  if (!ta) return CYC_ERR_ARG;
-  cyc_table* t = ta;
-  auto bad = [&](const char* m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  if (!tb) return bad("null table");
-  if (!pair_counts) return bad("null pair_counts");
-  if (const char* why = compare_args_bad(ta, tb, k_lo, k_hi)) return bad(why);
-  if (reinterpret_cast<uintptr_t>(d_diff) % 8) return bad("d_diff is not 8-byte aligned");
-  const int64_t nk = k_hi - k_lo, P = t->P, rows = t->row_hi - t->row_lo;
-  return table_guarded(t, [&]() -> int {
-    DeviceGuard dg(t->device);
-    const CompareTiles r = compare_tiles(t, tb, k_lo, k_hi, ignore_loopback, d_diff, false);
-    const std::vector<unsigned long long>& cnt = r.cnt;
-    // ValueCounts (comparisontable.go:109-123): a pair is the Items' equalsDict (:26-36) unless it is an
-    // ignored loopback; the table answers the pairs (s in its rows, every d)
-    int64_t differ = 0, self_differ = 0;
-    for (int64_t d = 0; d < P; d++) differ += int64_t(cnt[size_t(nk * P + d)]), self_differ += int64_t(cnt[size_t((nk + 1) * P + d)]);
-    pair_counts[2] = ignore_loopback ? rows : 0;
-    pair_counts[1] = differ - (ignore_loopback ? self_differ : 0);
-    pair_counts[0] = rows * P - pair_counts[1] - pair_counts[2];
-    compare_jobs_by_dst(t, r, k_lo, nk, ignore_loopback, slot_counts, dst_counts);
-    return (int)CYC_OK;
-  });
+  return ta ? table_compare(ta, tb, k_lo, k_hi, ignore_loopback, pair_counts, slot_counts, dst_counts, d_diff) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_pod_compare(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t* src_pairs,
                           int64_t* dst_pairs, int64_t* src_slots, int64_t* dst_slots) {
-  if (!ta) return CYC_ERR_ARG;
-  cyc_table* t = ta;
-  auto bad = [&](const char* m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  if (const char* why = compare_args_bad(ta, tb, k_lo, k_hi)) return bad(why);
-  if (!src_pairs && !dst_pairs && !src_slots && !dst_slots) return bad("no output requested");
-  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, rows = t->row_hi - t->row_lo, il = ignore_loopback ? 1 : 0;
-  return table_guarded(t, [&]() -> int {
-    DeviceGuard dg(t->device);
-    const CompareTiles r = compare_tiles(t, tb, k_lo, k_hi, ignore_loopback, nullptr, src_pairs || src_slots);
-    const unsigned long long* self = r.cnt.data() + (nk + 1) * P;  // whether the pair (d, d) differs
-    // the pairs (ValueCounts, as cyc_table_compare): of destination d over the table's sources, of source s over
-    // every destination; the loopback pair is ignored whether it differs or not
-    for (int64_t d = 0; dst_pairs && d < P; d++) {
-      int64_t* o = dst_pairs + d * 3;
-      o[2] = il && d >= t->row_lo && d < t->row_hi ? 1 : 0;
-      o[1] = int64_t(r.cnt[size_t(nk * P + d)]) - (il ? int64_t(self[d]) : 0);
-      o[0] = rows - o[1] - o[2];
-    }
-    const int64_t src_stride = int64_t(t->wa) * 64;  // (TileArgs::src_cnt: source-minor)
-    for (int64_t i = 0; src_pairs && i < rows; i++) {
-      int64_t* o = src_pairs + i * 3;
-      o[2] = il;
-      o[1] = int64_t(r.src[size_t(nk * src_stride + i)]) - (il ? int64_t(self[t->row_lo + i]) : 0);
-      o[0] = P - o[1] - o[2];
-    }
-    compare_jobs_by_dst(t, r, k_lo, nk, ignore_loopback, nullptr, dst_slots);
-    // per job and source: a's jobs of slot kk are the destinations whose status is not NONE, the loopback cell is
-    // ignored when (s, kk) is a job of a
-    for (int64_t kk = 0; src_slots && kk < nk; kk++) {
-      int64_t jobs = 0;
-      for (int64_t d = 0; d < P; d++) jobs += r.sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE;
-      for (int64_t i = 0; i < rows; i++) {
-        int64_t* o = src_slots + (i * nk + kk) * 3;
-        o[2] = il && r.sa[size_t((t->row_lo + i) * K + k_lo + kk)] != CYC_JOB_NONE ? 1 : 0;
-        o[1] = int64_t(r.src[size_t(kk * src_stride + i)]);
-        o[0] = jobs - o[1] - o[2];
-      }
-    }
-    return (int)CYC_OK;
-  });
+  return ta ? table_pod_compare(ta, tb, k_lo, k_hi, ignore_loopback, src_pairs, dst_pairs, src_slots, dst_slots) : (int)CYC_ERR_ARG;
 }
-
-// ---------------------------------------------------------------- counts and comparison per pod-group pair
-constexpr int64_t GROUP_CELLS_MAX = int64_t(1) << 27;  // n_groups^2 * slots of one call
-
-// The checks the two group entry points share; nullptr when the arguments are fine.
-static const char* group_args_bad(const cyc_table* t, const int32_t* group_of, int64_t G, int64_t k_lo, int64_t k_hi, std::string& why) {
-  if (!group_of) return "null group_of";
-  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return "slot range out of bounds";
-  if (G < 1) return "n_groups must be at least 1";
-  if (G > GROUP_CELLS_MAX || G * G * std::max<int64_t>(k_hi - k_lo, 1) > GROUP_CELLS_MAX)
-    return "n_groups^2 * slots exceeds the limit of 134217728 (2^27)";
-  for (int64_t p = 0; p < int64_t(t->P); p++)
-    if (group_of[p] < -1 || group_of[p] >= G) {
-      why = "group_of[" + std::to_string(p) + "] = " + std::to_string(group_of[p]) + " is neither -1 nor a group in [0, " +
-            std::to_string(G) + ")";
-      return why.c_str();
-    }
-  return nullptr;
-}
-
-// What k_table_group_tiles takes of a grouping (GroupArgs, dev_table.hpp), from one walk over the pods: the
-// (group, mask) entries of every source word of the table in pod order, the groups of every block row of 16
-// source words and block column of 1024 destinations numbered in order of appearance, and the group sizes
-// for the host-side terms.
-extern "C++" {
-struct GroupTables {
-  std::vector<uint32_t> ent_ptr{0}, ent_grp, ent_loc, row_ptr, row_grp, dst_loc, col_ptr, col_grp;
-  std::vector<uint64_t> ent_mask;
-  std::vector<int64_t> n_src, n_dst;  // pods of a group among the table's sources, among all destinations
-  DevBuf dev[10];
-
-  GroupTables(const cyc_table* t, const int32_t* group_of, int64_t G) : n_src(size_t(G), 0), n_dst(size_t(G), 0) {
-    constexpr uint32_t NONE = ~0u;
-    const size_t n = size_t(G);
-    std::vector<uint32_t> word_of(n, NONE), ent_of(n), blk_of(n, NONE), loc_of(n);
-    for (uint32_t j = 0; j < t->wa; j++) {
-      if (j % TT_WORDS == 0) row_ptr.push_back(uint32_t(row_grp.size()));
-      for (uint32_t b = 0; b < 64; b++) {
-        const int64_t s = int64_t(t->w0 + j) * 64 + b;
-        if (s < t->row_lo || s >= t->row_hi || group_of[s] < 0) continue;
-        const uint32_t g = uint32_t(group_of[s]);
-        n_src[g]++;
-        if (word_of[g] != j) {
-          if (blk_of[g] != j / TT_WORDS) {
-            blk_of[g] = j / TT_WORDS, loc_of[g] = uint32_t(row_grp.size()) - row_ptr.back();
-            row_grp.push_back(g);
-          }
-          word_of[g] = j, ent_of[g] = uint32_t(ent_grp.size());
-          ent_grp.push_back(g), ent_loc.push_back(loc_of[g]), ent_mask.push_back(0);
-        }
-        ent_mask[ent_of[g]] |= 1ull << b;
-      }
-      ent_ptr.push_back(uint32_t(ent_grp.size()));
-    }
-    row_ptr.push_back(uint32_t(row_grp.size()));
-    std::fill(blk_of.begin(), blk_of.end(), NONE);
-    dst_loc.assign(t->P, 0);
-    for (uint32_t d = 0; d < t->P; d++) {
-      if (d % (TT_WORDS * 64) == 0) col_ptr.push_back(uint32_t(col_grp.size()));
-      if (group_of[d] < 0) continue;
-      const uint32_t g = uint32_t(group_of[d]);
-      n_dst[g]++;
-      if (blk_of[g] != d / (TT_WORDS * 64)) {
-        blk_of[g] = d / (TT_WORDS * 64), loc_of[g] = uint32_t(col_grp.size()) - col_ptr.back();
-        col_grp.push_back(g);
-      }
-      dst_loc[d] = loc_of[g];
-    }
-    col_ptr.push_back(uint32_t(col_grp.size()));
-  }
-
-  // (asynchronous: the vectors live until the caller has synchronised the stream)
-  template <class T>
-  const T* put(int i, const T* v, size_t n, hipStream_t st) {
-    dev[i].alloc(std::max<size_t>(n * sizeof(T), 16));
-    if (n) HIPCHK(hipMemcpyAsync(dev[i].p, v, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return dev[i].as<T>();
-  }
-  GroupArgs args(const TileArgs& tile, const int32_t* group_of, int64_t G, hipStream_t st) {
-    GroupArgs g{};
-    g.t = tile, g.G = uint32_t(G);
-    g.ent_ptr = put(0, ent_ptr.data(), ent_ptr.size(), st);
-    g.ent_mask = put(1, ent_mask.data(), ent_mask.size(), st);
-    g.ent_grp = put(2, ent_grp.data(), ent_grp.size(), st);
-    g.ent_loc = put(3, ent_loc.data(), ent_loc.size(), st);
-    g.row_ptr = put(4, row_ptr.data(), row_ptr.size(), st);
-    g.row_grp = put(5, row_grp.data(), row_grp.size(), st);
-    g.dst_grp = put(6, group_of, tile.P, st);
-    g.dst_loc = put(7, dst_loc.data(), dst_loc.size(), st);
-    g.col_ptr = put(8, col_ptr.data(), col_ptr.size(), st);
-    g.col_grp = put(9, col_grp.data(), col_grp.size(), st);
-    return g;
-  }
-};
-}  // extern "C++"
 
 int cyc_table_group_counts(cyc_table* t, const int32_t* group_of, int64_t n_groups, int64_t k_lo, int64_t k_hi, int64_t* ingress,
                            int64_t* egress, int64_t* combined, int64_t* no_job) {
-  if (!t) return CYC_ERR_ARG;
-  auto bad = [&](const std::string& m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  std::string why;
-  if (const char* m = group_args_bad(t, group_of, n_groups, k_lo, k_hi, why)) return bad(m);
-  if (!ingress && !egress && !combined && !no_job) return bad("no output requested");
-  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
-  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, G = n_groups, GG = G * G, rows = t->row_hi - t->row_lo;
-  int64_t* out[3] = {ingress, egress, combined};
-  for (int x = 0; x < 3; x++)
-    if (out[x]) std::fill(out[x], out[x] + GG * nk * 6, int64_t(0));
-  if (no_job) std::fill(no_job, no_job + GG, int64_t(0));
-  if (!nk || !P) return (int)CYC_OK;
-  return table_guarded(t, [&]() -> int {
-    DeviceGuard dg(t->device);
-    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    // allowed cells [nk][3][G][G] of Ingress, Egress, Combined
-    const uint64_t n_cnt = uint64_t(nk) * 3 * GG;
-    std::vector<unsigned long long> cnt(n_cnt, 0);
-    std::vector<uint8_t> st(size_t(P) * K);
-    GroupTables gt(t, group_of, G);
-    DevBuf d_cnt;
-    if (rows) {
-      d_cnt.alloc(n_cnt * 8);
-      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
-      GroupArgs a = gt.args(tile_args(t, k_lo, k_hi), group_of, G, t->stream);
-      a.t.cnt = d_cnt.as<unsigned long long>();
-      k_table_group_tiles<false><<<tile_grid(t), 1024, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
-    }
-    HIPCHK(hipMemcpyAsync(st.data(), t->status, st.size(), hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    // the status-only terms, as cyc_table_counts': per (destination group, slot) the destinations of each
-    // status, times the sources of the source group
-    std::vector<int64_t> by_status(size_t(G) * nk * 4, 0);  // [gd][kk][cyc_job_status]
-    for (int64_t d = 0; d < P; d++)
-      if (group_of[d] >= 0)
-        for (int64_t kk = 0; kk < nk; kk++) by_status[size_t((group_of[d] * nk + kk) * 4 + (st[size_t(d * K + k_lo + kk)] & 3))]++;
-    for (int64_t gs = 0; gs < G; gs++) {
-      const int64_t ns = gt.n_src[size_t(gs)];
-      if (!ns) continue;
-      for (int64_t gd = 0; gd < G; gd++) {
-        if (!gt.n_dst[size_t(gd)]) continue;
-        for (int64_t kk = 0; kk < nk; kk++) {
-          const int64_t* s = &by_status[size_t((gd * nk + kk) * 4)];
-          const int64_t valid = ns * s[CYC_JOB_VALID], bpp = ns * s[CYC_JOB_BAD_PORT_PROTOCOL], bnp = ns * s[CYC_JOB_BAD_NAMED_PORT];
-          const size_t at = size_t(((gs * G + gd) * nk + kk) * 6);
-          for (int x = 0; x < 3; x++) {
-            if (!out[x]) continue;
-            const int64_t allowed = int64_t(cnt[size_t((kk * 3 + x) * GG + gs * G + gd)]);
-            int64_t* o = out[x] + at;
-            o[CYC_CONN_ALLOWED] = allowed, o[CYC_CONN_BLOCKED] = valid - allowed;
-            if (x == 1) o[CYC_CONN_UNKNOWN] = bpp + bnp;
-            else o[CYC_CONN_INVALID_PORT_PROTOCOL] = bpp, o[CYC_CONN_INVALID_NAMED_PORT] = bnp;
-          }
-          if (no_job) no_job[gs * G + gd] += ns * s[CYC_JOB_NONE];
-        }
-      }
-    }
-    return (int)CYC_OK;
-  });
+  return t ? table_group_counts(t, group_of, n_groups, k_lo, k_hi, ingress, egress, combined, no_job) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_group_compare(cyc_table* ta, cyc_table* tb, const int32_t* group_of, int64_t n_groups, int64_t k_lo, int64_t k_hi,
                             int ignore_loopback, int64_t* pair_counts, int64_t* slot_counts) {
-  if (!ta) return CYC_ERR_ARG;
-  cyc_table* t = ta;
-  auto bad = [&](const std::string& m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  if (!tb) return bad("null table");
-  if (!pair_counts) return bad("no output requested");
-  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition ||
-      ta->row_lo != tb->row_lo || ta->row_hi != tb->row_hi)
-    return bad("cannot compare tables of different devices, shapes, partitions or rows");
-  std::string why;
-  if (const char* m = group_args_bad(t, group_of, n_groups, k_lo, k_hi, why)) return bad(m);
-  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
-  const int64_t nk = k_hi - k_lo, P = t->P, K = t->K, G = n_groups, GG = G * G, rows = t->row_hi - t->row_lo;
-  std::fill(pair_counts, pair_counts + GG * 3, int64_t(0));
-  if (slot_counts) std::fill(slot_counts, slot_counts + GG * nk * 3, int64_t(0));
-  if (!P) return (int)CYC_OK;
-  return table_guarded(t, [&]() -> int {
-    DeviceGuard dg(t->device);
-    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    // [nk + 1][G][G]: differing cells per slot, then the differing pairs; then [G]: differing pairs (d, d)
-    const uint64_t n_cnt = uint64_t(nk + 1) * GG + G;
-    std::vector<unsigned long long> cnt(n_cnt, 0);
-    std::vector<uint8_t> sa(size_t(P) * K);
-    GroupTables gt(t, group_of, G);
-    if (rows) {
-      DevBuf d_cnt;
-      d_cnt.alloc(n_cnt * 8);
-      HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_cnt * 8, t->stream));
-      GroupArgs a = gt.args(tile_args(t, k_lo, k_hi), group_of, G, t->stream);
-      a.t.b = TablePlanes{tb->in, tb->eg, tb->status};
-      a.t.ignore_loopback = ignore_loopback ? 1u : 0u;
-      a.t.cnt = d_cnt.as<unsigned long long>();
-      k_table_group_tiles<true><<<tile_grid(t), 1024, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_cnt * 8, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipMemcpyAsync(sa.data(), ta->status, sa.size(), hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipStreamSynchronize(t->stream));  // (d_cnt is freed after it)
-    }
-    // the terms of cyc_table_compare, per group pair: jobs[gd][kk] = destinations of the group where a holds a
-    // job, loop[g][kk] = those among the table's sources (the loopback cells)
-    std::vector<int64_t> jobs(size_t(G) * nk, 0), loop(size_t(G) * nk, 0);
-    if (rows)
-      for (int64_t d = 0; d < P; d++)
-        if (group_of[d] >= 0)
-          for (int64_t kk = 0; kk < nk; kk++)
-            if (sa[size_t(d * K + k_lo + kk)] != CYC_JOB_NONE) {
-              jobs[size_t(group_of[d] * nk + kk)]++;
-              if (ignore_loopback && d >= t->row_lo && d < t->row_hi) loop[size_t(group_of[d] * nk + kk)]++;
-            }
-    for (int64_t gs = 0; gs < G; gs++) {
-      const int64_t ns = gt.n_src[size_t(gs)];
-      if (!ns) continue;
-      for (int64_t gd = 0; gd < G; gd++) {
-        const int64_t self = gs == gd ? 1 : 0;
-        int64_t* p = pair_counts + (gs * G + gd) * 3;
-        p[2] = ignore_loopback ? self * ns : 0;
-        p[1] = int64_t(cnt[size_t(nk * GG + gs * G + gd)]) - (ignore_loopback ? self * int64_t(cnt[size_t((nk + 1) * GG + gs)]) : 0);
-        p[0] = ns * gt.n_dst[size_t(gd)] - p[1] - p[2];
-        for (int64_t kk = 0; slot_counts && kk < nk; kk++) {
-          int64_t* v = slot_counts + ((gs * G + gd) * nk + kk) * 3;
-          v[2] = self * loop[size_t(gs * nk + kk)];
-          v[1] = int64_t(cnt[size_t(kk * GG + gs * G + gd)]);
-          v[0] = ns * jobs[size_t(gd * nk + kk)] - v[1] - v[2];
-        }
-      }
-    }
-    return (int)CYC_OK;
-  });
-}
-
-// ---------------------------------------------------------------- which cells: find and compare_find
-static_assert(sizeof(cyc_cell) == 16, "cyc_cell is one 16-byte store");
-constexpr uint32_t FIND_LDS_SLOTS = 32;      // 2 KB of words per slot and wave: up to here they fit 64 KB of LDS
-constexpr uint32_t FIND_SCRATCH_GRID = 1024;  // beyond, the words live in global scratch and the grid is capped
-constexpr uint32_t FIND_EMIT_GRID = 1u << 20;  // waves of the emit kernel; further (source word, block) items by stride
-
-// The shared body of the two entry points: tb == nullptr is find (view, code_mask), otherwise compare_find
-// (ignore_loopback).  The callers have checked what only one of them takes.
-static int table_find(cyc_table* t, cyc_table* tb, int view, uint32_t code_mask, int ignore_loopback, int64_t k_lo, int64_t k_hi,
-                      int64_t s_from, cyc_cell* cells, int64_t cap, int64_t* n, int64_t* s_next, int64_t* total) {
-  auto bad = [&](const std::string& m) {
-    t->err = m;
-    return (int)CYC_ERR_ARG;
-  };
-  if (!n || !s_next || !total) return bad("null n, s_next or total");
-  *n = 0, *total = 0, *s_next = s_from;
-  if (k_lo < 0 || k_hi > int64_t(t->K) || k_lo > k_hi) return bad("slot range out of bounds");
-  if (!table_whole(t)) return bad("ingress cells need destinations inside the table's rows");
-  if (s_from < t->row_lo || s_from > t->row_hi) return bad("s_from outside the table's rows");
-  if (cap < 0) return bad("negative cap");
-  if (!cells && cap > 0) return bad("null cells");
-  const bool count_only = !cells;
-  const int64_t nk = k_hi - k_lo, rows = t->row_hi - s_from;
-  if (!nk && !count_only) *s_next = t->row_hi;
-  if (!nk || !rows) return (int)CYC_OK;
-  return table_guarded(t, [&]() -> int {
-    DeviceGuard dg(t->device);
-    if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    const bool cmp = tb != nullptr;
-    FindArgs a{};
-    a.t = tile_args(t, k_lo, k_hi);
-    if (cmp) a.t.b = TablePlanes{tb->in, tb->eg, tb->status};
-    a.t.ignore_loopback = ignore_loopback ? 1u : 0u;
-    a.view = uint32_t(view), a.code_mask = code_mask;
-    a.NB = (t->W + TT_WORDS - 1) / TT_WORDS;
-    a.bx0 = uint32_t((s_from / 64 - t->w0) / TT_WORDS);
-    // ---- pass 1: matches per (destination block, source), then per source
-    const uint64_t n_src = uint64_t(t->row_hi - t->row_lo), n_stw = uint64_t(nk) * t->W * 2, n_blk = uint64_t(a.NB) * n_src;
-    DevBuf d_cnt, d_stw, d_blk;
-    d_cnt.alloc(n_src * 8), d_stw.alloc(n_stw * 8), d_blk.alloc(n_blk * 8);
-    HIPCHK(hipMemsetAsync(d_cnt.p, 0, n_src * 8, t->stream));  // (the sources before pass 1's first block)
-    a.n_src = uint32_t(n_src);
-    a.t.cnt = d_cnt.as<unsigned long long>();
-    a.stw = d_stw.as<uint64_t>();
-    a.blk = d_blk.as<unsigned long long>();
-    const dim3 grid((t->wa + TT_WORDS - 1) / TT_WORDS - a.bx0, a.NB);
-    if (cmp) {
-      k_find_status_words<true><<<grid1(n_stw / 2, 256), 256, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-      k_table_find_count<true><<<grid, 1024, 0, t->stream>>>(a);
-    } else {
-      k_find_status_words<false><<<grid1(n_stw / 2, 256), 256, 0, t->stream>>>(a);
-      HIPCHK(hipGetLastError());
-      k_table_find_count<false><<<grid, 1024, 0, t->stream>>>(a);
-    }
-    HIPCHK(hipGetLastError());
-    k_table_find_scan<<<grid1(n_src - uint64_t(a.bx0) * TT_WORDS * 64, 256), 256, 0, t->stream>>>(a);
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned long long> cnt(n_src);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n_src * 8, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    // ---- the page: sources [s_from, s_next) are the longest run whose records fit into cap
-    const unsigned long long* c = cnt.data() + (s_from - t->row_lo);  // c[i]: source s_from + i
-    for (int64_t i = 0; i < rows; i++) *total += int64_t(c[i]);
-    if (count_only) return (int)CYC_OK;
-    std::vector<unsigned long long> offs(1, 0);  // offs[i]: first record of source s_from + i
-    int64_t page = 0;
-    while (page < rows && offs.back() + c[page] <= (unsigned long long)cap) offs.push_back(offs.back() + c[page++]);
-    if (!page)
-      return bad("source " + std::to_string(s_from) + " alone has " + std::to_string(c[0]) + " matching cells, more than cap " +
-                 std::to_string(cap));
-    *s_next = s_from + page;
-    *n = int64_t(offs.back());
-    if (!*n) return (int)CYC_OK;
-    // ---- pass 2: the records of the page
-    DevBuf d_offs, d_out, d_scratch;
-    d_offs.alloc(offs.size() * 8), d_out.alloc(uint64_t(*n) * sizeof(cyc_cell));
-    HIPCHK(hipMemcpyAsync(d_offs.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, t->stream));
-    a.s_from = uint32_t(s_from), a.s_next = uint32_t(*s_next);
-    a.offs = d_offs.as<unsigned long long>();
-    a.out = d_out.as<uint4>();
-    // a wave per (source word of the page, destination block); those without a match leave at once
-    const uint64_t items = uint64_t((*s_next + 63) / 64 - s_from / 64) * a.NB;
-    uint32_t waves = uint32_t(std::min<uint64_t>(items, FIND_EMIT_GRID));
-    size_t lds = size_t(nk) * 4 * 64 * 8;
-    if (nk > FIND_LDS_SLOTS) {
-      waves = std::min(waves, FIND_SCRATCH_GRID);
-      d_scratch.alloc(uint64_t(waves) * lds);
-      a.scratch = d_scratch.as<uint64_t>();
-      lds = 0;
-    }
-    if (cmp) k_table_find_emit<true><<<waves, 64, lds, t->stream>>>(a);
-    else k_table_find_emit<false><<<waves, 64, lds, t->stream>>>(a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(cells, d_out.p, uint64_t(*n) * sizeof(cyc_cell), hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    return (int)CYC_OK;
-  });
+  return ta ? table_group_compare(ta, tb, group_of, n_groups, k_lo, k_hi, ignore_loopback, pair_counts, slot_counts) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_find(cyc_table* t, int view, uint32_t code_mask, int64_t k_lo, int64_t k_hi, int64_t s_from, cyc_cell* cells, int64_t cap,
                    int64_t* n, int64_t* s_next, int64_t* total) {
   if (!t) return CYC_ERR_ARG;
-  if (view != CYC_VIEW_INGRESS && view != CYC_VIEW_EGRESS && view != CYC_VIEW_COMBINED) return t->err = "unknown view", (int)CYC_ERR_ARG;
-  if (!code_mask || code_mask >> 6) return t->err = "code_mask must name codes 0..5", (int)CYC_ERR_ARG;
+  if (const char* m = view_bad(view)) return table_bad(t, m);
+  if (!code_mask || code_mask >> 6) return table_bad(t, "code_mask must name codes 0..5");
   return table_find(t, nullptr, view, code_mask, 0, k_lo, k_hi, s_from, cells, cap, n, s_next, total);
 }
 
 int cyc_table_compare_find(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k_hi, int ignore_loopback, int64_t s_from, cyc_cell* cells,
                            int64_t cap, int64_t* n, int64_t* s_next, int64_t* total) {
   if (!ta) return CYC_ERR_ARG;
-  if (!tb) return ta->err = "null table", (int)CYC_ERR_ARG;
-  if (ta->device != tb->device || ta->P != tb->P || ta->K != tb->K || ta->partition != tb->partition || ta->row_lo != tb->row_lo ||
-      ta->row_hi != tb->row_hi)
-    return ta->err = "cannot compare tables of different devices, shapes, partitions or rows", (int)CYC_ERR_ARG;
+  if (const char* m = pair_bad(ta, tb)) return table_bad(ta, m);
   return table_find(ta, tb, CYC_VIEW_COMBINED, 0, ignore_loopback, k_lo, k_hi, s_from, cells, cap, n, s_next, total);
 }
 

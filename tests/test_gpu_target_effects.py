@@ -169,7 +169,7 @@ def test_seventy_targets_on_one_pod():
 
 # ---- several batches and word windows: the scratch cap (dev_effects.hpp, EFF_SCRATCH_CAP) lowered for the process
 def _batch_bytes(eng, dr, targets, words):
-    """The batch buffers of `targets` targets built `words` words at a time (engine.hip, target_effects): per target
+    """The batch buffers of `targets` targets built `words` words at a time (effects.hpp, target_effects): per target
     and word D row words, per target its population counts (D for ingress, a slot's for egress) and sole counts."""
     D, nk = max(eng.shape["descriptors"], 1), eng.shape["slots"]
     return targets * (((nk if dr else D) + nk) * 8 + D * 8 * words)
