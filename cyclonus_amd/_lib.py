@@ -62,6 +62,8 @@ EXPORTS = [
     "cyc_table_group_compare",
     "cyc_table_pod_counts",
     "cyc_table_pod_compare",
+    "cyc_table_adjacency",
+    "cyc_table_reach",
     "cyc_table_shape",
     "cyc_table_error",
     "cyc_table_destroy",
@@ -108,6 +110,11 @@ EFFECTS = ("allowing", "denying", "sole_allowing", "sole_denying")
 VIEW_INGRESS, VIEW_EGRESS, VIEW_COMBINED = 0, 1, 2
 VIEWS = {"ingress": VIEW_INGRESS, "egress": VIEW_EGRESS, "combined": VIEW_COMBINED}
 
+# cyc_reach_direction (cyc_table_adjacency, cyc_table_reach)
+REACH_FROM, REACH_TO = 0, 1
+REACH_DIRECTIONS = {"from": REACH_FROM, "to": REACH_TO}
+REACH_WORDS_MAX = 1 << 24  # seed sets x 64-pod words of one cyc_table_reach call
+
 # CYC_POD_CODES: a row of cyc_table_pod_counts is the six cyc_connectivity codes, then the cells without a job
 POD_CODES = 7
 
@@ -152,6 +159,19 @@ def code_mask(codes) -> int:
             raise ValueError(f"not a cyc_connectivity code: {c}")
         mask |= 1 << int(c)
     return mask
+
+
+def seed_arrays(seed_sets):
+    """The seed sets of cyc_table_reach (a sequence of sequences of pod indices) as (seed_off i64 [n + 1], seeds i32)."""
+    import numpy as np
+
+    sets = [np.asarray(s, np.int64).reshape(-1) for s in seed_sets]
+    off = np.zeros(len(sets) + 1, np.int64)
+    off[1:] = np.cumsum([len(s) for s in sets])
+    seeds = np.concatenate(sets) if sets else np.zeros(0, np.int64)
+    if len(seeds) and (seeds.min() < -2**31 or seeds.max() >= 2**31):
+        raise ValueError("a seed does not fit 32 bits")
+    return off, np.ascontiguousarray(seeds, np.int32)
 
 
 def pages(page, s_from, s_end):
@@ -214,6 +234,8 @@ def lib():
         L.cyc_table_group_compare.argtypes = [vp, vp, vp, i64, i64, i64, i, vp, vp]
         L.cyc_table_pod_counts.argtypes = [vp, i, i64, i64, vp, vp]
         L.cyc_table_pod_compare.argtypes = [vp, vp, i64, i64, i, vp, vp, vp, vp]
+        L.cyc_table_adjacency.argtypes = [vp, i64, i64, i, vp]
+        L.cyc_table_reach.argtypes = [vp, i64, i64, i, vp, vp, i64, i64, vp, vp, vp]
         L.cyc_table_shape.argtypes = [vp, ctypes.POINTER(i64), i]
         L.cyc_table_error.argtypes = [vp]
         L.cyc_table_error.restype = cp

@@ -59,13 +59,15 @@
 #include "dev_gather.hpp"
 #include "dev_table.hpp"
 #include "dev_effects.hpp"
+#include "dev_reach.hpp"
 
-// Host side: context, planner, enqueueing, the bodies of the effects and table calls; the C ABI below
+// Host side: context, planner, enqueueing, the bodies of the effects, table and reach calls; the C ABI below
 #include "ctx.hpp"
 #include "plan.hpp"
 #include "enqueue.hpp"
 #include "effects.hpp"
 #include "table.hpp"
+#include "reach.hpp"
 
 extern "C" {
 
@@ -511,6 +513,15 @@ int cyc_table_compare_find(cyc_table* ta, cyc_table* tb, int64_t k_lo, int64_t k
   if (!ta) return CYC_ERR_ARG;
   if (const char* m = pair_bad(ta, tb)) return table_bad(ta, m);
   return table_find(ta, tb, CYC_VIEW_COMBINED, 0, ignore_loopback, k_lo, k_hi, s_from, cells, cap, n, s_next, total);
+}
+
+int cyc_table_adjacency(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction, uint64_t* d_adj) {
+  return t ? table_adjacency(t, k_lo, k_hi, direction, d_adj) : (int)CYC_ERR_ARG;
+}
+
+int cyc_table_reach(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction, const int64_t* seed_off, const int32_t* seeds, int64_t n_sets,
+                    int64_t max_hops, uint64_t* reach, int32_t* hops, int64_t* levels) {
+  return t ? table_reach(t, k_lo, k_hi, direction, seed_off, seeds, n_sets, max_hops, reach, hops, levels) : (int)CYC_ERR_ARG;
 }
 
 void cyc_table_destroy(cyc_table* t) {

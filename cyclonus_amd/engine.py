@@ -499,3 +499,36 @@ class DeviceTable:
 
     def compare_find_all(self, other, k_lo=0, k_hi=None, ignore_loopback=False, cap=None):
         yield from _lib.pages(lambda s: self.compare_find(other, k_lo, k_hi, ignore_loopback, s, cap), self.row_lo, self.row_hi)
+
+    # ---- multi-hop reachability (cyc_table_adjacency, cyc_table_reach)
+    def adjacency(self, direction="from", k_lo=0, k_hi=None, d_out=None):
+        """cyc_table_adjacency: the edges of slots [k_lo, k_hi) as a bit plane [P, W] on the table's device: "from" row s
+        bit d, "to" row d bit s set iff s -> d is a Combined of allowed in some slot.  Returns a torch int64 tensor that
+        owns the plane, or with d_out (a device pointer to write the plane to) that pointer."""
+        k_hi = self.slots if k_hi is None else k_hi
+        adj = None
+        if d_out is None:
+            import torch
+
+            adj = torch.empty((self.pods, self.words), dtype=torch.int64, device=f"cuda:{self.device}")
+        ptr = d_out if d_out is not None else (adj.data_ptr() if adj.numel() else None)
+        self._check(lib().cyc_table_adjacency(self._t, int(k_lo), int(k_hi), int(_lib.REACH_DIRECTIONS.get(direction, direction)),
+                                              ctypes.c_void_p(ptr)))
+        return d_out if d_out is not None else adj
+
+    def reach(self, seed_sets, direction="from", k_lo=0, k_hi=None, max_hops=-1, want=("reach", "hops", "levels")):
+        """cyc_table_reach: breadth-first search over those edges for every seed set (a sequence of sequences of pod
+        indices) at once: {"reach": u64 [n, W] bit p = reached, "hops": i32 [n, P] least number of edges from a seed
+        ("to": to a seed), -1 = not within max_hops (negative: no bound), "levels": i64 [n] the largest hop value,
+        -1 for an empty set}."""
+        k_hi = self.slots if k_hi is None else k_hi
+        off, seeds = _lib.seed_arrays(seed_sets)
+        n = len(off) - 1
+        ok = n * max(self.words, 1) <= _lib.REACH_WORDS_MAX  # (the library refuses the rest and writes nothing)
+        shape = {"reach": ((n, self.words), np.uint64), "hops": ((n, self.pods), np.int32), "levels": ((n,), np.int64)}
+        out = {x: np.zeros(shape[x][0] if ok else (0,), shape[x][1]) for x in want}
+        # (empty numpy arrays still have a data pointer: an empty output is never the NULL the library refuses)
+        ptr = [ctypes.c_void_p(out[x].ctypes.data) if x in out else None for x in ("reach", "hops", "levels")]
+        self._check(lib().cyc_table_reach(self._t, int(k_lo), int(k_hi), int(_lib.REACH_DIRECTIONS.get(direction, direction)),
+                                          ctypes.c_void_p(off.ctypes.data), ctypes.c_void_p(seeds.ctypes.data), n, int(max_hops), *ptr))
+        return out

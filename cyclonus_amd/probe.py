@@ -406,6 +406,91 @@ class PlaneCells:
     def compare_find_all(self, other, k_lo=0, k_hi=None, ignore_loopback=False, cap=None):
         yield from _lib.pages(lambda s: self.compare_find(other, k_lo, k_hi, ignore_loopback, s, cap), 0, self.status.shape[0])
 
+    # Multi-hop reachability (cyc_table_adjacency / cyc_table_reach): an edge s -> d is a Combined of allowed in some
+    # slot of the range, read off the unpacked bits and the status array; then a plain queue per seed set.
+    def _edge_pairs(self, k_lo, k_hi):
+        """(s, d) of every edge, s-major and without repeats: some slot k of [k_lo, k_hi) has status[d][k] VALID, the
+        ingress bit (d, k, s) and the egress bit (s, k, d) set: cells()' Combined == allowed.  The egress words that
+        hold no bit are skipped, so sparse planes of many pods stay cheap.  Kept per slot range: the planes of a
+        PlaneCells are not expected to change under it."""
+        P = self.status.shape[0]
+        if not 0 <= k_lo <= k_hi <= self.status.shape[1]:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "slot range out of bounds")
+        memo = self.__dict__.setdefault("_pairs", {})
+        if (k_lo, k_hi) in memo:
+            return memo[k_lo, k_hi]
+        bit, found = np.arange(64, dtype=np.uint64), [np.zeros(0, np.int64)]
+        for k in range(k_lo, k_hi):
+            rows, words = np.nonzero(self.egress[:, k, :])
+            for lo in range(0, len(rows), 1 << 16):
+                r, w = rows[lo:lo + (1 << 16)], words[lo:lo + (1 << 16)]
+                i, b = np.nonzero((self.egress[r, k, w][:, None] >> bit) & np.uint64(1))
+                s, d = r[i], w[i] * 64 + b
+                s, d = s[d < P], d[d < P]  # (plane bits at or beyond P)
+                ingress = (self.ingress[d, k, s // 64] >> (s % 64).astype(np.uint64)) & np.uint64(1)
+                ok = (self.status[d, k] == _lib.JOB_VALID) & ingress.astype(bool)
+                found.append(s[ok] * P + d[ok])
+        e = np.unique(np.concatenate(found))
+        memo[k_lo, k_hi] = e // max(P, 1), e % max(P, 1)
+        return memo[k_lo, k_hi]
+
+    @staticmethod
+    def _direction(direction):
+        d = _lib.REACH_DIRECTIONS.get(direction, direction)
+        if d not in (_lib.REACH_FROM, _lib.REACH_TO):
+            raise _lib.CyclonusError(_lib.ERR_ARG, "unknown direction")
+        return d
+
+    def adjacency(self, direction="from", k_lo=0, k_hi=None):
+        """cyc_table_adjacency: u64 [P, W]; "from": row s bit d, "to": row d bit s set iff there is an edge s -> d."""
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        r, c = self._edge_pairs(k_lo, k_hi)
+        if self._direction(direction) == _lib.REACH_TO:
+            r, c = c, r
+        P = self.status.shape[0]
+        out = np.zeros((P, (P + 63) // 64), np.uint64)
+        np.bitwise_or.at(out, (r, c // 64), np.uint64(1) << (c % 64).astype(np.uint64))
+        return out
+
+    def reach(self, seed_sets, direction="from", k_lo=0, k_hi=None, max_hops=-1, want=("reach", "hops", "levels")):
+        """cyc_table_reach: {"reach": u64 [n, W], "hops": i32 [n, P], "levels": i64 [n]} (DeviceTable.reach)."""
+        from collections import deque
+
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        P = self.status.shape[0]
+        a, b = self._edge_pairs(k_lo, k_hi)
+        if self._direction(direction) == _lib.REACH_TO:
+            a, b = b, a  # (a path to a seed is a path from it along the reversed edges)
+        off, seeds = _lib.seed_arrays(seed_sets)
+        bad = np.nonzero((seeds < 0) | (seeds >= P))[0]
+        if len(bad):
+            raise _lib.CyclonusError(_lib.ERR_ARG, f"seeds[{bad[0]}] = {seeds[bad[0]]} is not a pod in [0, {P})")
+        nbrs = [[] for _ in range(P)]
+        for p, q in zip(a.tolist(), b.tolist()):
+            nbrs[p].append(q)
+        n = len(off) - 1
+        hops = np.full((n, P), -1, np.int32)
+        for j in range(n):
+            h, queue = [-1] * P, deque()
+            for p in seeds[off[j]:off[j + 1]].tolist():
+                if h[p] < 0:
+                    h[p] = 0
+                    queue.append(p)
+            while queue:
+                p = queue.popleft()
+                if 0 <= max_hops <= h[p]:
+                    continue
+                for q in nbrs[p]:
+                    if h[q] < 0:
+                        h[q] = h[p] + 1
+                        queue.append(q)
+            hops[j] = h
+        reach = np.zeros((n, (P + 63) // 64), np.uint64)
+        j, p = np.nonzero(hops >= 0)
+        np.bitwise_or.at(reach, (j, p // 64), np.uint64(1) << (p % 64).astype(np.uint64))
+        out = {"reach": reach, "hops": hops, "levels": hops.max(axis=1, initial=-1).astype(np.int64)}
+        return {x: out[x] for x in want}
+
 
 class Table:
     """Lazy probe.Table over one probe config's slots of a verdict table (table.go:24-56).
@@ -528,6 +613,16 @@ class Table:
         cell = lambda c: f"{c.get(ALLOWED, 0)}/{sum(c.values())}"  # noqa: E731
         rows = [[name, cell(counts[name]["as_source"]), cell(counts[name]["as_destination"])] for name in self.items]
         return render(["", "as source", "as destination"], rows, row_line=False)
+
+    # Multi-hop: what the pods get to through other pods (the reference answers one hop at a time).
+    def reach(self, pods, direction: str = "from", max_hops: int = -1) -> dict:
+        """{pod: hops} for every pod reached from the seed pods ("ns/name" strings, or one) over edges that are a
+        Combined of allowed in some slot of the table: the least number of edges from a seed (direction "to": to a
+        seed; the seeds are 0), paths of at most max_hops edges (negative: no bound); searched by the cells source
+        (cyc_table_reach on the device for a DeviceTable)."""
+        seeds = [self.index[p] for p in ([pods] if isinstance(pods, str) else pods)]
+        hops = self.src.reach([seeds], direction, self.slots.start, self.slots.stop, max_hops, want=("hops",))["hops"][0]
+        return {p.pod_string(): int(hops[i]) for i, p in enumerate(self.resources.pods) if hops[i] >= 0}
 
     # table.go:58-156
     def render_ingress(self) -> str:

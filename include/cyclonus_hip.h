@@ -473,6 +473,43 @@ int cyc_table_pod_counts(cyc_table* t, int view /* cyc_view */, int64_t k_lo, in
  * slot_counts. */
 int cyc_table_pod_compare(cyc_table* a, cyc_table* b, int64_t k_lo, int64_t k_hi, int ignore_loopback,
                           int64_t* src_pairs, int64_t* dst_pairs, int64_t* src_slots, int64_t* dst_slots);
+/* ---- Multi-hop reachability: what a pod gets to through other pods and in how many hops; which pods get to it.
+ * The reference has no such summary.  There is an edge s -> d iff some slot k in [k_lo, k_hi) has
+ * status[d][k] == CYC_JOB_VALID, the ingress bit (d, k, s) and the egress bit (s, k, d) set: a Combined of
+ * CYC_CONN_ALLOWED (policy.go:123-125) with the codes of cyc_table_cells.  Plane bits at or beyond P and bits of
+ * non-VALID slots never make an edge; a loopback edge s -> s is kept in the adjacency plane and cannot change a reach
+ * result.  Accepted tables: one that answers every cell, i.e. a whole target-row table or a CYC_ROWS_SOURCE table
+ * over rows [0, P); any other table is refused with the text of a partial target-row table (reach over the shards
+ * of a partition is not offered).  Stream, lifetime, failures and plane alignment as for cyc_table_counts; neither
+ * call changes the table, the context, its options or cyc_last_*.  An unknown direction or a bad slot range:
+ * CYC_ERR_ARG.
+ *
+ * cyc_table_adjacency: one pass over the planes of the slot range into d_adj, a DEVICE plane [P][W], 8-byte aligned
+ * (or CYC_ERR_ARG naming d_adj), synchronous on the table's stream like cyc_table_compare's d_diff:
+ *   CYC_REACH_FROM  row s, bit d set iff there is an edge s -> d
+ *   CYC_REACH_TO    row d, bit s set iff there is an edge s -> d (the transpose)
+ * Bits at or beyond P are 0; exactly the plane's bytes are written; an empty slot range writes zeros. */
+typedef enum { CYC_REACH_FROM = 0, CYC_REACH_TO = 1 } cyc_reach_direction;
+int cyc_table_adjacency(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction /* cyc_reach_direction */, uint64_t* d_adj);
+/* Breadth-first search over those edges for n_sets seed sets at once.  Seed set j is
+ * seeds[seed_off[j] .. seed_off[j + 1]): pod indices, duplicates allowed, a set may be empty; seed_off has
+ * n_sets + 1 entries.  All arrays are host arrays, copied during the call.  max_hops >= 0 bounds the path length,
+ * max_hops < 0 runs to the fixpoint.  Outputs (host, each optional, at least one):
+ *   hops    [j * P + p]: CYC_REACH_FROM the least h >= 0 such that a path of h edges leads from some seed of set j
+ *           to p, CYC_REACH_TO from p to some seed of set j; seeds are 0; -1 when no path of at most max_hops
+ *           edges exists.
+ *   reach   [j * W + p / 64] bit p % 64 set iff hops >= 0; bits at or beyond P are 0.
+ *   levels  [j]: the largest hop value of set j, -1 for an empty set.
+ * Exactly the stated number of elements of each output is written, and only when the call succeeds; n_sets == 0
+ * writes nothing and returns CYC_OK.  The results are exact and the same from run to run.  The adjacency plane
+ * (P rows of W words rounded up to 16), three bitsets of n_sets * W words and, with hops, n_sets * P 32-bit values
+ * are device scratch of the call, freed before it returns; an allocation that fails is CYC_ERR_OOM with a message.
+ * Limit: n_sets * max(W, 1) <= 2^24 words (else CYC_ERR_ARG stating the limit).  Also CYC_ERR_ARG, each with its
+ * message: negative n_sets; NULL seed_off; a seed_off that does not start at 0 or decreases; NULL seeds when a set
+ * has a seed; a seed outside [0, P) (the message names the first bad index and its value); all outputs NULL. */
+int cyc_table_reach(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction /* cyc_reach_direction */,
+                    const int64_t* seed_off, const int32_t* seeds, int64_t n_sets, int64_t max_hops, uint64_t* reach,
+                    int32_t* hops, int64_t* levels);
 /* out[0..7] = pods, slots, words, row_lo, row_hi, partition, ingress window first word, window words */
 int cyc_table_shape(const cyc_table* t, int64_t* out, int n);
 const char* cyc_table_error(const cyc_table* t);

@@ -5,6 +5,7 @@
                                              pod_counts|pod_compare [n=2]   # n calls of one pass (for a rocprofv3 run)
     python scripts/table_counts_bench.py group [reps=3] [out=FILE]  # the group leg alone (below)
     python scripts/table_counts_bench.py pod [reps=3] [out=FILE]    # the pod leg alone (below)
+    python scripts/table_counts_bench.py reach [reps=3] [out=FILE]  # the reachability leg alone (below)
 
 In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
 drawn with another seed; then, min over reps of the synchronous calls,
@@ -29,6 +30,11 @@ reps of each:
   pod_compare  cyc_table_pod_compare, all four outputs, against cyc_table_compare without d_diff
 and once, as checks, the sum invariants: both arrays of either call summed over the pods are the whole-table results,
 and dst_slots is cyc_table_compare's dst_counts.
+The reachability leg (mode `reach`): every slot, interleaved with counts and the plain read, min over reps of each:
+  adjacency  cyc_table_adjacency into a device plane, both directions
+  reach      cyc_table_reach "from" for 1 seed set and for 64 seed sets of one random pod each, to the fixpoint: the
+             steps taken, the pods reached, the device scratch, the time split (a call without steps, one without hop
+             values and copy-back, the whole call) and the adjacency rows gathered against the bound of DESIGN.md
 """
 import json
 import os
@@ -197,6 +203,67 @@ if mode == "pod":
         f"{res['sources_with_a_different_pair']} as source, {res['destinations_with_a_different_pair']} as destination",
         json.dumps(res),
     ]
+    print("\n".join(lines))
+    if "out" in kw:
+        os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
+        with open(kw["out"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
+
+if mode == "reach":
+    # slots [0, K): the adjacency plane both ways next to counts and the plain read, then the search from 1 seed set and
+    # from 64 seed sets of one random pod each, to the fixpoint.  The library frees its scratch inside the call and reports
+    # no phases, so the split is taken from calls that leave a phase out: no step (max_hops = 0, levels alone), the steps
+    # without hop values or copy-back (levels alone), everything.
+    rng = np.random.default_rng(16)
+    seeds = [[int(p)] for p in rng.integers(0, P, 64)]
+    adj = torch.empty((P, W), dtype=torch.int64, device="cuda")
+    pitch = (W + 15) // 16 * 16
+    legs = {"counts": lambda: ta.counts(), "read2": lambda: read(1),
+            "adjacency_from": lambda: ta.adjacency("from", d_out=adj.data_ptr()), "adjacency_to": lambda: ta.adjacency("to", d_out=adj.data_ptr())}
+    for n in (1, 64):
+        legs[f"reach{n}_no_step"] = lambda n=n: ta.reach(seeds[:n], max_hops=0, want=("levels",))
+        legs[f"reach{n}_levels"] = lambda n=n: ta.reach(seeds[:n], want=("levels",))
+        legs[f"reach{n}"] = lambda n=n: ta.reach(seeds[:n])
+    got = {n: ta.reach(seeds[:n]) for n in (1, 64)}  # (warm-up, and the figures of the search)
+    for f in legs.values():
+        f()
+    ms = {n: float("inf") for n in legs}
+    for _ in range(reps):  # interleaved: every leg once per round
+        for n, f in legs.items():
+            ms[n] = min(ms[n], timed(f, 1))
+    # the edges: the set bits of the plane the last leg left in adj ("to"), counted through a byte table
+    ones = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64, device="cuda")
+    edges = sum(int(ones[adj[lo:lo + 2048].view(torch.uint8).long()].sum()) for lo in range(0, P, 2048))
+    res = {"config": config, "pods": P, "slots": K, "words": W, "plane_gb": round(plane_gb, 3), "reps": reps,
+           **{n + "_ms": v for n, v in ms.items()}, "adjacency_gb": P * W * 8 / 1e9, "edges_to_plane": edges,
+           "adjacency_from_over_read": ms["adjacency_from"] / ms["read2"], "adjacency_to_over_read": ms["adjacency_to"] / ms["read2"],
+           "adjacency_from_over_counts": ms["adjacency_from"] / ms["counts"], "adjacency_to_over_counts": ms["adjacency_to"] / ms["counts"]}
+    lines = [
+        f"# {config}: P {P}, K {K}, W {W}, slots [0, {K}); a plane is {plane_gb:.2f} GB, the adjacency plane {res['adjacency_gb']:.3f} GB; "
+        f"min of {reps} interleaved synchronous calls",
+        f"counts {ms['counts']:9.2f} ms   read of 2 planes {ms['read2']:9.2f} ms   adjacency from {ms['adjacency_from']:9.2f} ms "
+        f"({res['adjacency_from_over_read']:.2f} x read, {res['adjacency_from_over_counts']:.2f} x counts, {2 * plane_gb / ms['adjacency_from'] * 1e3:.0f} GB/s of 2 planes)   "
+        f"adjacency to {ms['adjacency_to']:9.2f} ms ({res['adjacency_to_over_read']:.2f} x read, {res['adjacency_to_over_counts']:.2f} x counts, "
+        f"{2 * plane_gb / ms['adjacency_to'] * 1e3:.0f} GB/s); edges in the plane {edges}",
+    ]
+    for n in (1, 64):
+        g = got[n]
+        reached = [int(x) for x in (g["hops"] >= 0).sum(axis=1)]
+        steps = int(g["levels"].max()) + 1  # (the last step finds nothing)
+        bound_gb = sum(reached) * pitch * 8 / 1e9  # rows gathered: every reached pod's row once per set
+        step_ms = ms[f"reach{n}_levels"] - ms[f"reach{n}_no_step"]
+        scratch_mb = (P * pitch * 8 + 3 * n * W * 8 + n * P * 4 + n * 8 + K * W * 16) / 1e6
+        res.update({f"reach{n}_steps": steps, f"reach{n}_levels_max": int(g["levels"].max()), f"reach{n}_reached_min": min(reached),
+                    f"reach{n}_reached_max": max(reached), f"reach{n}_reached_sum": sum(reached), f"reach{n}_rows_gb": bound_gb,
+                    f"reach{n}_bound_gb": n * P * pitch * 8 / 1e9, f"reach{n}_steps_ms": step_ms,
+                    f"reach{n}_hops_and_copy_ms": ms[f"reach{n}"] - ms[f"reach{n}_levels"], f"reach{n}_scratch_mb": scratch_mb})
+        lines.append(
+            f"reach from {n:2d} seed set(s) of one random pod, to the fixpoint: {ms[f'reach{n}']:9.2f} ms = adjacency and seeds {ms[f'reach{n}_no_step']:.2f} "
+            f"+ {steps} steps {step_ms:.2f} + hop values and copy-back {res[f'reach{n}_hops_and_copy_ms']:.2f}; pods reached {min(reached)} - {max(reached)} "
+            f"per set, deepest level {int(g['levels'].max())}; rows gathered {bound_gb:.2f} GB (bound {res[f'reach{n}_bound_gb']:.2f} GB: the plane once per set), "
+            f"{bound_gb / max(step_ms, 1e-9) * 1e3:.0f} GB/s over the steps; device scratch {scratch_mb:.0f} MB")
+    lines.append(json.dumps(res))
     print("\n".join(lines))
     if "out" in kw:
         os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
