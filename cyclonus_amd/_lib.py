@@ -64,6 +64,9 @@ EXPORTS = [
     "cyc_table_pod_compare",
     "cyc_table_adjacency",
     "cyc_table_reach",
+    "cyc_table_classes",
+    "cyc_table_classes_masked",
+    "cyc_table_cells_at",
     "cyc_table_shape",
     "cyc_table_error",
     "cyc_table_destroy",
@@ -236,6 +239,9 @@ def lib():
         L.cyc_table_pod_compare.argtypes = [vp, vp, i64, i64, i, vp, vp, vp, vp]
         L.cyc_table_adjacency.argtypes = [vp, i64, i64, i, vp]
         L.cyc_table_reach.argtypes = [vp, i64, i64, i, vp, vp, i64, i64, vp, vp, vp]
+        L.cyc_table_classes.argtypes = [vp, i, i64, i64, vp, vp, vp, vp]
+        L.cyc_table_classes_masked.argtypes = [vp, i, i64, i64, vp, vp, vp, vp, ctypes.c_uint64, vp]
+        L.cyc_table_cells_at.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp]
         L.cyc_table_shape.argtypes = [vp, ctypes.POINTER(i64), i]
         L.cyc_table_error.argtypes = [vp]
         L.cyc_table_error.restype = cp

@@ -60,14 +60,16 @@
 #include "dev_table.hpp"
 #include "dev_effects.hpp"
 #include "dev_reach.hpp"
+#include "dev_classes.hpp"
 
-// Host side: context, planner, enqueueing, the bodies of the effects, table and reach calls; the C ABI below
+// Host side: context, planner, enqueueing, the bodies of the effects, table, reach and class calls; the C ABI below
 #include "ctx.hpp"
 #include "plan.hpp"
 #include "enqueue.hpp"
 #include "effects.hpp"
 #include "table.hpp"
 #include "reach.hpp"
+#include "classes.hpp"
 
 extern "C" {
 
@@ -522,6 +524,20 @@ int cyc_table_adjacency(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction,
 int cyc_table_reach(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction, const int64_t* seed_off, const int32_t* seeds, int64_t n_sets,
                     int64_t max_hops, uint64_t* reach, int32_t* hops, int64_t* levels) {
   return t ? table_reach(t, k_lo, k_hi, direction, seed_off, seeds, n_sets, max_hops, reach, hops, levels) : (int)CYC_ERR_ARG;
+}
+
+int cyc_table_classes(cyc_table* t, int view, int64_t k_lo, int64_t k_hi, int32_t* src_class, int32_t* dst_class, int64_t* n_src, int64_t* n_dst) {
+  return t ? table_classes(t, view, k_lo, k_hi, src_class, dst_class, n_src, n_dst, ~0ull, nullptr) : (int)CYC_ERR_ARG;
+}
+
+int cyc_table_classes_masked(cyc_table* t, int view, int64_t k_lo, int64_t k_hi, int32_t* src_class, int32_t* dst_class, int64_t* n_src,
+                             int64_t* n_dst, uint64_t hash_mask, int64_t* stats) {
+  return t ? table_classes(t, view, k_lo, k_hi, src_class, dst_class, n_src, n_dst, hash_mask, stats) : (int)CYC_ERR_ARG;
+}
+
+int cyc_table_cells_at(cyc_table* t, const int32_t* srcs, int64_t n_s, const int32_t* dsts, int64_t n_d, int64_t k_lo, int64_t k_hi,
+                       uint8_t* ingress, uint8_t* egress, uint8_t* combined) {
+  return t ? table_cells_at(t, srcs, n_s, dsts, n_d, k_lo, k_hi, ingress, egress, combined) : (int)CYC_ERR_ARG;
 }
 
 void cyc_table_destroy(cyc_table* t) {

@@ -532,3 +532,40 @@ class DeviceTable:
         self._check(lib().cyc_table_reach(self._t, int(k_lo), int(k_hi), int(_lib.REACH_DIRECTIONS.get(direction, direction)),
                                           ctypes.c_void_p(off.ctypes.data), ctypes.c_void_p(seeds.ctypes.data), n, int(max_hops), *ptr))
         return out
+
+    # ---- connectivity classes (cyc_table_classes, cyc_table_cells_at)
+    def classes(self, view="combined", k_lo=0, k_hi=None, want=("src", "dst"), hash_mask=None, stats=False):
+        """cyc_table_classes: the pods partitioned by equal rows ("src") and equal columns ("dst") of `view`'s cell codes
+        over slots [k_lo, k_hi): {"src": i32 [P] class of every pod as a source, "n_src": int, "dst": ..., "n_dst": ...}
+        with the classes numbered by their smallest pod.  hash_mask (cyc_table_classes_masked): the row hash is ANDed
+        with it before the pods are grouped; stats: also "stats": i64 [4] = verification rounds and failed pods for
+        sources, then for destinations."""
+        k_hi = self.slots if k_hi is None else k_hi
+        cls = {x: np.zeros(self.pods, np.int32) for x in want}
+        cnt = {x: ctypes.c_int64(0) for x in want}
+        st = np.zeros(4, np.int64)
+        ptr = [ctypes.c_void_p(cls[x].ctypes.data) if x in cls else None for x in ("src", "dst")]
+        ptr += [ctypes.byref(cnt[x]) if x in cnt else None for x in ("src", "dst")]
+        v = int(_lib.VIEWS.get(view, view))
+        if hash_mask is None and not stats:
+            self._check(lib().cyc_table_classes(self._t, v, int(k_lo), int(k_hi), *ptr))
+        else:
+            mask = (1 << 64) - 1 if hash_mask is None else int(hash_mask)
+            self._check(lib().cyc_table_classes_masked(self._t, v, int(k_lo), int(k_hi), *ptr, mask, ctypes.c_void_p(st.ctypes.data) if stats else None))
+        out = {}
+        for x in want:
+            out[x], out["n_" + x] = cls[x], int(cnt[x].value)
+        if stats:
+            out["stats"] = st
+        return out
+
+    def cells_at(self, sources, dests, k_lo=0, k_hi=None, want=("ingress", "egress", "combined")):
+        """cyc_table_cells_at: {name: u8 [n_s, n_d, k]} of cyc_connectivity codes for the listed sources and
+        destinations (pod indices in any order, duplicates allowed)."""
+        k_hi = self.slots if k_hi is None else k_hi
+        s, d = np.ascontiguousarray(sources, np.int32).reshape(-1), np.ascontiguousarray(dests, np.int32).reshape(-1)
+        out = {n: np.zeros((len(s), len(d), max(k_hi - k_lo, 0)), np.uint8) for n in want}
+        ptr = [ctypes.c_void_p(out[n].ctypes.data) if n in out else None for n in ("ingress", "egress", "combined")]
+        self._check(lib().cyc_table_cells_at(self._t, ctypes.c_void_p(s.ctypes.data), len(s), ctypes.c_void_p(d.ctypes.data), len(d),
+                                             int(k_lo), int(k_hi), *ptr))
+        return out

@@ -491,6 +491,44 @@ class PlaneCells:
         out = {"reach": reach, "hops": hops, "levels": hops.max(axis=1, initial=-1).astype(np.int64)}
         return {x: out[x] for x in want}
 
+    # Connectivity classes (cyc_table_classes / cyc_table_cells_at), cell by cell: the pods grouped by the bytes of their
+    # row (as sources) or column (as destinations) of the view's cell codes, numbered by first occurrence.
+    def classes(self, view="combined", k_lo=0, k_hi=None, want=("src", "dst"), hash_mask=None, stats=False):
+        """cyc_table_classes: {"src": i32 [P], "n_src": int, "dst": i32 [P], "n_dst": int} (DeviceTable.classes;
+        hash_mask and stats belong to the device's way of getting there and are ignored)."""
+        view = {v: n for n, v in _lib.VIEWS.items()}.get(view, view)
+        if view not in _lib.VIEWS:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "unknown view")
+        P, K = self.status.shape
+        k_hi = K if k_hi is None else k_hi
+        if not 0 <= k_lo <= k_hi <= K:
+            raise _lib.CyclonusError(_lib.ERR_ARG, "slot range out of bounds")
+        _, chunks = self._source_chunks()
+        out = {}
+        for side in want:
+            seen, cls = {}, np.zeros(P, np.int32)
+            for lo, hi in chunks:
+                if side == "src":
+                    codes = self.cells(lo, hi, 0, P, k_lo, k_hi, want=(view,))[view]  # [pods of the chunk, d, k]
+                else:
+                    codes = self.cells(0, P, lo, hi, k_lo, k_hi, want=(view,))[view].transpose(1, 0, 2)  # [pods of the chunk, s, k]
+                for p in range(lo, hi):
+                    cls[p] = seen.setdefault(np.ascontiguousarray(codes[p - lo]).tobytes(), len(seen))
+            out[side], out["n_" + side] = cls, len(seen)
+        return out
+
+    def cells_at(self, sources, dests, k_lo=0, k_hi=None, want=("ingress", "egress", "combined")):
+        """cyc_table_cells_at: {name: u8 [n_s, n_d, k]} for lists of pods."""
+        P, K = self.status.shape
+        k_hi = K if k_hi is None else k_hi
+        s, d = np.asarray(sources, np.int64).reshape(-1), np.asarray(dests, np.int64).reshape(-1)
+        for name, x in (("srcs", s), ("dsts", d)):
+            bad = np.nonzero((x < 0) | (x >= P))[0]
+            if len(bad):
+                raise _lib.CyclonusError(_lib.ERR_ARG, f"{name}[{bad[0]}] = {x[bad[0]]} is not a pod in [0, {P})")
+        cells = self.cells(0, P, 0, P, k_lo, k_hi, want=want)
+        return {n: np.ascontiguousarray(cells[n][s][:, d]) for n in want}
+
 
 class Table:
     """Lazy probe.Table over one probe config's slots of a verdict table (table.go:24-56).
@@ -623,6 +661,35 @@ class Table:
         seeds = [self.index[p] for p in ([pods] if isinstance(pods, str) else pods)]
         hops = self.src.reach([seeds], direction, self.slots.start, self.slots.stop, max_hops, want=("hops",))["hops"][0]
         return {p.pod_string(): int(hops[i]) for i, p in enumerate(self.resources.pods) if hops[i] >= 0}
+
+    # The lossless summary: the pods that behave alike, and the table of one representative per class.
+    def _classes(self, view):
+        if view not in _lib.VIEWS:
+            raise ValueError(f"invalid view: {view}")
+        c = self.src.classes(view, self.slots.start, self.slots.stop)
+        members = {side: [[] for _ in range(c["n_" + side])] for side in ("src", "dst")}
+        for side in ("src", "dst"):
+            for p, x in enumerate(c[side].tolist()):
+                members[side][x].append(p)
+        return members
+
+    def classes(self, view: str = "combined") -> dict:
+        """{"sources": [[pods of class 0], ...], "destinations": [...]}: the pods ("ns/name", in plane order) whose jobs'
+        Ingress, Egress or Combined (`view`) agree towards every pod, and from every pod, over the table's slots;
+        classes in the order of their first pod; found by the cells source (cyc_table_classes on the device for a
+        DeviceTable)."""
+        m, pods = self._classes(view), self.resources.pods
+        return {name: [[pods[p].pod_string() for p in c] for c in m[side]] for name, side in (("sources", "src"), ("destinations", "dst"))}
+
+    def render_class_table(self, view: str = "combined") -> str:
+        """Source classes by destination classes, each labelled by its first pod and " (+N)" for its N other members;
+        a cell holds the view's short string per slot for the two first pods, "-" for a slot without a job."""
+        m, pods = self._classes(view), self.resources.pods
+        label = lambda c: pods[c[0]].pod_string() + (f" (+{len(c) - 1})" if len(c) > 1 else "")  # noqa: E731
+        codes = self.src.cells_at([c[0] for c in m["src"]], [c[0] for c in m["dst"]], self.slots.start, self.slots.stop, want=(view,))[view]
+        short = lambda x: "-" if x == _lib.CONN_NO_JOB else short_string(_CONN[x])  # noqa: E731
+        rows = [[label(c)] + ["\n".join(short(int(x)) for x in codes[i, j]) for j in range(len(m["dst"]))] for i, c in enumerate(m["src"])]
+        return render([""] + [label(c) for c in m["dst"]], rows, row_line=len(self.slots) > 1)
 
     # table.go:58-156
     def render_ingress(self) -> str:

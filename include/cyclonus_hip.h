@@ -510,6 +510,46 @@ int cyc_table_adjacency(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction 
 int cyc_table_reach(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction /* cyc_reach_direction */,
                     const int64_t* seed_off, const int32_t* seeds, int64_t n_sets, int64_t max_hops, uint64_t* reach,
                     int32_t* hops, int64_t* levels);
+/* ---- Connectivity classes: the lossless summary of a table.  The reference prints every pod (table.go:58-156);
+ * most pods of a real cluster behave exactly like many others, and the whole table is a class x class table
+ * (cyc_table_cells_at over one representative per class) plus the two index arrays below.  Unlike the engine's
+ * identity classes these are read off the table, so they exist for a wrapped table too and are as coarse as the
+ * enforced behaviour.  The code of a cell is the code cyc_table_cells returns for `view` (a cyc_view) at (s, d, k),
+ * CYC_CONN_NO_JOB included; the slot range is [k_lo, k_hi).
+ *   source classes       pods p and q are in one class iff code(p, d, k) == code(q, d, k) for every destination d
+ *                        in [0, P) and every k of the range
+ *   destination classes  p and q are in one class iff code(s, p, k) == code(s, q, k) for every source s and every k
+ * A non-VALID job's code depends on (d, k) only: it never separates sources, and it separates destinations exactly
+ * when the status gives the view another code (under CYC_VIEW_EGRESS both invalid kinds are `unknown` and do not
+ * separate; under the other two views they do).  Plane bits at or beyond P and plane bits of non-VALID (d, k)
+ * never matter; loopback is not special.  Class ids are canonical: classes are numbered 0, 1, ... in the order of
+ * their smallest member pod, so class[0] == 0, and the ids are the same from run to run.  An empty slot range puts
+ * every pod in class 0 on both sides; with P == 0 nothing is written to the arrays and the counts are 0.
+ * Outputs (host, each optional, at least one): src_class, dst_class int32 [P]; n_src, n_dst the numbers of classes.
+ * Exactly the stated number of elements is written, and only when the call succeeds.  Accepted tables as for
+ * cyc_table_reach (one that answers every cell; any other is refused with the text of a partial target-row table).
+ * Stream, lifetime, plane alignment as for cyc_table_counts; the call changes neither the table, the context, its
+ * options nor cyc_last_*.  CYC_ERR_ARG, each with its message: an unknown view, a bad slot range, all outputs NULL.
+ * Rows are hashed on the device, grouped on the host and then compared word for word on the device, so the result
+ * is exact whatever the hash does.  Device scratch of the call, freed before it returns: per side one bit plane of
+ * P rows of W words rounded up to 16, 20 bytes a pod, and for sources 16 bytes per (slot, word); an allocation
+ * that fails is CYC_ERR_OOM with the byte count. */
+int cyc_table_classes(cyc_table* t, int view /* cyc_view */, int64_t k_lo, int64_t k_hi, int32_t* src_class,
+                      int32_t* dst_class, int64_t* n_src, int64_t* n_dst);
+/* Diagnostic twin: the row hash is ANDed with hash_mask before pods are grouped (0 groups by nothing but the
+ * verification).  The four outputs above do not depend on hash_mask; cyc_table_classes is this call with ~0 and no
+ * stats.  stats: optional host int64[4] = {verification rounds for sources, pods that failed a verification as
+ * sources, the same two for destinations}. */
+int cyc_table_classes_masked(cyc_table* t, int view /* cyc_view */, int64_t k_lo, int64_t k_hi, int32_t* src_class,
+                             int32_t* dst_class, int64_t* n_src, int64_t* n_dst, uint64_t hash_mask, int64_t* stats);
+/* cyc_table_cells for lists of pods instead of ranges (a class table is cells_at(representatives, representatives)):
+ * out index ((i * n_d + j) * nk + k - k_lo) for srcs[i], dsts[j]; duplicates and any order allowed; an empty list
+ * or slot range writes nothing.  The lists are host arrays, copied during the call.  Row requirements per output as
+ * cyc_table_cells, for every listed pod.  CYC_ERR_ARG, each with its message: a bad slot range, a negative count, a
+ * NULL list with a positive count, a list entry outside [0, P) (the message names the list, the first bad index and
+ * its value), all outputs NULL.  Outputs are written only when the call succeeds. */
+int cyc_table_cells_at(cyc_table* t, const int32_t* srcs, int64_t n_s, const int32_t* dsts, int64_t n_d, int64_t k_lo,
+                       int64_t k_hi, uint8_t* ingress, uint8_t* egress, uint8_t* combined);
 /* out[0..7] = pods, slots, words, row_lo, row_hi, partition, ingress window first word, window words */
 int cyc_table_shape(const cyc_table* t, int64_t* out, int n);
 const char* cyc_table_error(const cyc_table* t);

@@ -6,6 +6,7 @@
     python scripts/table_counts_bench.py group [reps=3] [out=FILE]  # the group leg alone (below)
     python scripts/table_counts_bench.py pod [reps=3] [out=FILE]    # the pod leg alone (below)
     python scripts/table_counts_bench.py reach [reps=3] [out=FILE]  # the reachability leg alone (below)
+    python scripts/table_counts_bench.py classes [reps=3] [out=FILE]  # the connectivity-class leg alone (below)
 
 In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
 drawn with another seed; then, min over reps of the synchronous calls,
@@ -35,6 +36,11 @@ The reachability leg (mode `reach`): every slot, interleaved with counts and the
   reach      cyc_table_reach "from" for 1 seed set and for 64 seed sets of one random pod each, to the fixpoint: the
              steps taken, the pods reached, the device scratch, the time split (a call without steps, one without hop
              values and copy-back, the whole call) and the adjacency rows gathered against the bound of DESIGN.md
+The class leg (mode `classes`): every slot, Combined view, interleaved with counts, the adjacency pass both ways and the
+plain read, min over reps of each:
+  classes   cyc_table_classes_masked with stats for sources only, destinations only and both; the numbers of classes,
+            the verification rounds and the pods that failed one
+  cells_at  cyc_table_cells_at over one representative per class (the class table)
 """
 import json
 import os
@@ -264,6 +270,52 @@ if mode == "reach":
             f"per set, deepest level {int(g['levels'].max())}; rows gathered {bound_gb:.2f} GB (bound {res[f'reach{n}_bound_gb']:.2f} GB: the plane once per set), "
             f"{bound_gb / max(step_ms, 1e-9) * 1e3:.0f} GB/s over the steps; device scratch {scratch_mb:.0f} MB")
     lines.append(json.dumps(res))
+    print("\n".join(lines))
+    if "out" in kw:
+        os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
+        with open(kw["out"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
+
+if mode == "classes":
+    # slots [0, K), Combined: sources only, destinations only, both (with stats), the class table through cells_at, next
+    # to counts, the adjacency pass both ways (one pass over the planes where a side of classes makes two per slot) and
+    # the plain read.
+    adj = torch.empty((P, W), dtype=torch.int64, device="cuda")
+    pitch = (W + 15) // 16 * 16
+    got = ta.classes("combined", stats=True)  # (warm-up, and the figures)
+    reps_s, reps_d = np.unique(got["src"], return_index=True)[1], np.unique(got["dst"], return_index=True)[1]
+    legs = {"counts": lambda: ta.counts(), "read2": lambda: read(1),
+            "adjacency_from": lambda: ta.adjacency("from", d_out=adj.data_ptr()), "adjacency_to": lambda: ta.adjacency("to", d_out=adj.data_ptr()),
+            "classes_src": lambda: ta.classes("combined", want=("src",), stats=True),
+            "classes_dst": lambda: ta.classes("combined", want=("dst",), stats=True),
+            "classes": lambda: ta.classes("combined", stats=True),
+            "cells_at": lambda: ta.cells_at(reps_s, reps_d)}
+    for f in legs.values():
+        f()
+    ms = {n: float("inf") for n in legs}
+    for _ in range(reps):  # interleaved: every leg once per round
+        for n, f in legs.items():
+            ms[n] = min(ms[n], timed(f, 1))
+    table = ta.cells_at(reps_s, reps_d, want=("combined",))["combined"]
+    scratch_mb = (P * pitch * 8 + P * 20 + K * W * 16) / 1e6
+    res = {"config": config, "pods": P, "slots": K, "words": W, "plane_gb": round(plane_gb, 3), "reps": reps,
+           **{n + "_ms": v for n, v in ms.items()}, "n_src": got["n_src"], "n_dst": got["n_dst"], "stats": [int(x) for x in got["stats"]],
+           "classes_over_counts": ms["classes"] / ms["counts"], "classes_src_over_counts": ms["classes_src"] / ms["counts"],
+           "classes_dst_over_counts": ms["classes_dst"] / ms["counts"], "classes_over_read": ms["classes"] / ms["read2"],
+           "class_table_cells": int(table.size), "class_table_allowed": int((table == CONN_ALLOWED).sum()), "scratch_mb": scratch_mb}
+    lines = [
+        f"# {config}: P {P}, K {K}, W {W}, slots [0, {K}), Combined; a plane is {plane_gb:.2f} GB, the view plane of a slot {P * pitch * 8 / 1e9:.3f} GB; "
+        f"min of {reps} interleaved synchronous calls",
+        f"counts {ms['counts']:9.2f} ms   read of 2 planes {ms['read2']:9.2f} ms   adjacency from {ms['adjacency_from']:9.2f} ms   to {ms['adjacency_to']:9.2f} ms",
+        f"classes: sources {ms['classes_src']:9.2f} ms ({res['classes_src_over_counts']:.2f} x counts)   destinations {ms['classes_dst']:9.2f} ms "
+        f"({res['classes_dst_over_counts']:.2f} x counts)   both {ms['classes']:9.2f} ms ({res['classes_over_counts']:.2f} x counts, {res['classes_over_read']:.2f} x read)",
+        f"{got['n_src']} source classes and {got['n_dst']} destination classes of {P} pods; verification rounds and failed pods "
+        f"(sources, destinations) {res['stats']}; device scratch of a side {scratch_mb:.0f} MB",
+        f"cells_at over the representatives ({len(reps_s)} x {len(reps_d)} x {K} cells, three views): {ms['cells_at']:9.2f} ms; "
+        f"allowed Combined cells of the class table {res['class_table_allowed']} of {res['class_table_cells']}",
+        json.dumps(res),
+    ]
     print("\n".join(lines))
     if "out" in kw:
         os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
