@@ -639,6 +639,15 @@ int cyc_get_option(cyc_ctx* c, const char* name, int64_t* value) {
   else if (n == "pl_wave_active") {
     if (!c->prepared) return need_prepare();
     *value = c->route.pl_wave ? 1 : 0;
+  } else if (n == "port_bits_active") {
+    if (!c->prepared) return need_prepare();
+    *value = c->route.port_bits ? 1 : 0;
+  } else if (n == "slot_words_active") {
+    if (!c->prepared) return need_prepare();
+    *value = c->route.slot_words ? 1 : 0;
+  } else if (n == "uni_desc_active") {
+    if (!c->prepared) return need_prepare();
+    *value = c->prep.uni_desc ? 1 : 0;
   } else if (n == "class_inplace_active") {
     if (!c->prepared || !c->range.valid) return fail(c, CYC_ERR_ARG, "class_inplace_active: run a probe first");
     *value = c->route.inplace ? 1 : 0;

@@ -682,7 +682,9 @@ int cyc_last_emit(cyc_ctx* ctx, char* name, size_t cap, int64_t* launches);
  *   "plvt_max_mb" 1024 (default) / 0..1048576: the largest per-pod label table (PLVT) the sparse pod-peer
  *                 rows build on the device; beyond it (0: always) they gather through each pod's label set
  * cyc_get_option also reports "launch" (the graphs mode in effect), "row_phases_active" (the last
- * run's phases: 2, or 0), "front_fused_active", "pl_wave_active" (needs cyc_probe_prepare),
+ * run's phases: 2, or 0), "front_fused_active", "pl_wave_active", "port_bits_active" (the port table's
+ * descriptor bit rows: at most 32 descriptors), "slot_words_active" (the slot words are built) and
+ * "uni_desc_active" (every pod has the same VALID descriptor in each slot; these four need cyc_probe_prepare),
  * "class_inplace_active" and "emit_interleave_active" (the routes in effect; they need a run),
  * "plvt_active", "ip_iv_rows" and "ip_range_rows" (the current range plan's
  * interval-built and range-built IP rows), "pod_post_rows" and "pod_scan_rows" (its sparse pod-peer rows built

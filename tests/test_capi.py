@@ -233,7 +233,8 @@ def test_option_table():
             assert e.get_option(name) == default, name
     # unprepared reads, options at their defaults
     fails("pod_words: call cyc_probe_prepare first", e.get_option, "pod_words")
-    fails("pl_wave_active: call cyc_probe_prepare first", e.get_option, "pl_wave_active")
+    for name in ("pl_wave_active", "port_bits_active", "slot_words_active", "uni_desc_active"):
+        fails(f"{name}: call cyc_probe_prepare first", e.get_option, name)
     fails("class_inplace_active: run a probe first", e.get_option, "class_inplace_active")
     assert e.get_option("launch") == 1
     for name in ("front_fused_active", "plvt_active", "ip_iv_rows", "ip_range_rows", "pod_post_rows", "pod_scan_rows", "row_phases_active"):
