@@ -64,6 +64,8 @@ EXPORTS = [
     "cyc_table_pod_compare",
     "cyc_table_adjacency",
     "cyc_table_reach",
+    "cyc_table_closure",
+    "cyc_table_zones",
     "cyc_table_classes",
     "cyc_table_classes_masked",
     "cyc_table_cells_at",
@@ -113,7 +115,7 @@ EFFECTS = ("allowing", "denying", "sole_allowing", "sole_denying")
 VIEW_INGRESS, VIEW_EGRESS, VIEW_COMBINED = 0, 1, 2
 VIEWS = {"ingress": VIEW_INGRESS, "egress": VIEW_EGRESS, "combined": VIEW_COMBINED}
 
-# cyc_reach_direction (cyc_table_adjacency, cyc_table_reach)
+# cyc_reach_direction (cyc_table_adjacency, cyc_table_reach, cyc_table_closure)
 REACH_FROM, REACH_TO = 0, 1
 REACH_DIRECTIONS = {"from": REACH_FROM, "to": REACH_TO}
 REACH_WORDS_MAX = 1 << 24  # seed sets x 64-pod words of one cyc_table_reach call
@@ -239,6 +241,8 @@ def lib():
         L.cyc_table_pod_compare.argtypes = [vp, vp, i64, i64, i, vp, vp, vp, vp]
         L.cyc_table_adjacency.argtypes = [vp, i64, i64, i, vp]
         L.cyc_table_reach.argtypes = [vp, i64, i64, i, vp, vp, i64, i64, vp, vp, vp]
+        L.cyc_table_closure.argtypes = [vp, i64, i64, i, vp, vp]
+        L.cyc_table_zones.argtypes = [vp, i64, i64, vp, vp, vp, vp]
         L.cyc_table_classes.argtypes = [vp, i, i64, i64, vp, vp, vp, vp]
         L.cyc_table_classes_masked.argtypes = [vp, i, i64, i64, vp, vp, vp, vp, ctypes.c_uint64, vp]
         L.cyc_table_cells_at.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp]

@@ -60,15 +60,17 @@
 #include "dev_table.hpp"
 #include "dev_effects.hpp"
 #include "dev_reach.hpp"
+#include "dev_closure.hpp"
 #include "dev_classes.hpp"
 
-// Host side: context, planner, enqueueing, the bodies of the effects, table, reach and class calls; the C ABI below
+// Host side: context, planner, enqueueing, the bodies of the effects, table, reach, closure and class calls; the C ABI below
 #include "ctx.hpp"
 #include "plan.hpp"
 #include "enqueue.hpp"
 #include "effects.hpp"
 #include "table.hpp"
 #include "reach.hpp"
+#include "closure.hpp"
 #include "classes.hpp"
 
 extern "C" {
@@ -524,6 +526,14 @@ int cyc_table_adjacency(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction,
 int cyc_table_reach(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction, const int64_t* seed_off, const int32_t* seeds, int64_t n_sets,
                     int64_t max_hops, uint64_t* reach, int32_t* hops, int64_t* levels) {
   return t ? table_reach(t, k_lo, k_hi, direction, seed_off, seeds, n_sets, max_hops, reach, hops, levels) : (int)CYC_ERR_ARG;
+}
+
+int cyc_table_closure(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction, uint64_t* d_closure, int64_t* n_reach) {
+  return t ? table_closure(t, k_lo, k_hi, direction, d_closure, n_reach) : (int)CYC_ERR_ARG;
+}
+
+int cyc_table_zones(cyc_table* t, int64_t k_lo, int64_t k_hi, int32_t* zone, int64_t* n_zones, int64_t* n_from, int64_t* n_to) {
+  return t ? table_zones(t, k_lo, k_hi, zone, n_zones, n_from, n_to) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_classes(cyc_table* t, int view, int64_t k_lo, int64_t k_hi, int32_t* src_class, int32_t* dst_class, int64_t* n_src, int64_t* n_dst) {

@@ -533,6 +533,45 @@ class DeviceTable:
                                           ctypes.c_void_p(off.ctypes.data), ctypes.c_void_p(seeds.ctypes.data), n, int(max_hops), *ptr))
         return out
 
+    # ---- all pairs: the transitive closure and the zones (cyc_table_closure, cyc_table_zones)
+    def closure(self, direction="from", k_lo=0, k_hi=None, d_out=None, want=("plane", "n_reach")):
+        """cyc_table_closure: the reflexive transitive closure of adjacency()'s edges: {"plane": a bit plane [P, W] on the
+        table's device, "from": row p bit q set iff a path leads from p to q, "to": from q to p (a torch int64 tensor that
+        owns the plane, or with d_out, a device pointer to write the plane to, that pointer), "n_reach": i64 [P] the set
+        bits of every row}."""
+        k_hi = self.slots if k_hi is None else k_hi
+        out, ptr = {}, None
+        if d_out is not None:
+            out["plane"], ptr = d_out, d_out
+        elif "plane" in want:
+            import torch
+
+            out["plane"] = torch.empty((self.pods, self.words), dtype=torch.int64, device=f"cuda:{self.device}")
+            # (a tensor without elements has no pointer to refuse: the count keeps the call from being without output)
+            ptr = out["plane"].data_ptr() if out["plane"].numel() else None
+        if "n_reach" in want or (ptr is None and "plane" in want):
+            out["n_reach"] = np.zeros(self.pods, np.int64)
+        n = ctypes.c_void_p(out["n_reach"].ctypes.data) if "n_reach" in out else None
+        self._check(lib().cyc_table_closure(self._t, int(k_lo), int(k_hi), int(_lib.REACH_DIRECTIONS.get(direction, direction)),
+                                            ctypes.c_void_p(ptr), n))
+        return {x: out[x] for x in out if x in want or (x == "plane" and d_out is not None)}
+
+    def zones(self, k_lo=0, k_hi=None, want=("zone", "n_from", "n_to")):
+        """cyc_table_zones: {"zone": i32 [P] the zone of every pod (pods are in one zone iff each reaches the other; zones
+        numbered by their smallest pod), "n_zones": int, "n_from": i64 [P] the pods a pod reaches, "n_to": i64 [P] the
+        pods that reach it, each with the pod itself}."""
+        k_hi = self.slots if k_hi is None else k_hi
+        dt = {"zone": np.int32, "n_from": np.int64, "n_to": np.int64}
+        out = {x: np.zeros(self.pods, dt[x]) for x in want if x in dt}
+        nz = ctypes.c_int64(0)
+        # (empty numpy arrays still have a data pointer: an empty output is never the NULL the library refuses)
+        p = {x: ctypes.c_void_p(out[x].ctypes.data) if x in out else None for x in dt}
+        self._check(lib().cyc_table_zones(self._t, int(k_lo), int(k_hi), p["zone"], ctypes.byref(nz) if "zone" in want or "n_zones" in want else None,
+                                          p["n_from"], p["n_to"]))
+        if "zone" in want or "n_zones" in want:
+            out["n_zones"] = int(nz.value)
+        return out
+
     # ---- connectivity classes (cyc_table_classes, cyc_table_cells_at)
     def classes(self, view="combined", k_lo=0, k_hi=None, want=("src", "dst"), hash_mask=None, stats=False):
         """cyc_table_classes: the pods partitioned by equal rows ("src") and equal columns ("dst") of `view`'s cell codes

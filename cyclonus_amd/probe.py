@@ -491,6 +491,33 @@ class PlaneCells:
         out = {"reach": reach, "hops": hops, "levels": hops.max(axis=1, initial=-1).astype(np.int64)}
         return {x: out[x] for x in want}
 
+    # All pairs (cyc_table_closure / cyc_table_zones): plain Warshall over the packed adjacency rows, a pivot pod a step;
+    # the zones by the mutual test on the unpacked matrix.
+    def closure(self, direction="from", k_lo=0, k_hi=None, d_out=None, want=("plane", "n_reach")):
+        """cyc_table_closure: {"plane": u64 [P, W], "n_reach": i64 [P]} (DeviceTable.closure; d_out belongs to the
+        device and is ignored)."""
+        k_hi = self.status.shape[1] if k_hi is None else k_hi
+        c = self.adjacency(direction, k_lo, k_hi)
+        P = c.shape[0]
+        p = np.arange(P)
+        c[p, p // 64] |= np.uint64(1) << (p % 64).astype(np.uint64)
+        for k in range(P):
+            through = (c[:, k // 64] >> np.uint64(k % 64)) & np.uint64(1) != 0  # the rows that reach the pivot
+            c[through] |= c[k]
+        out = {"plane": c, "n_reach": np.unpackbits(c.view(np.uint8), axis=1).sum(axis=1, dtype=np.int64).reshape(P)}
+        return {x: out[x] for x in want}
+
+    def zones(self, k_lo=0, k_hi=None, want=("zone", "n_from", "n_to")):
+        """cyc_table_zones: {"zone": i32 [P], "n_zones": int, "n_from": i64 [P], "n_to": i64 [P]} (DeviceTable.zones)."""
+        P = self.status.shape[0]
+        c = self.closure("from", k_lo, k_hi, want=("plane",))["plane"]
+        m = np.unpackbits(c.view(np.uint8), axis=1, bitorder="little")[:, :P].astype(bool).reshape(P, P)
+        first = (m & m.T).argmax(axis=1) if P else np.zeros(0, np.int64)  # the smallest pod a pod shares its zone with
+        heads = np.flatnonzero(first == np.arange(P))
+        out = {"zone": np.searchsorted(heads, first).astype(np.int32), "n_zones": len(heads),
+               "n_from": m.sum(axis=1, dtype=np.int64), "n_to": m.sum(axis=0, dtype=np.int64)}
+        return {x: out[x] for x in out if x in want or (x == "n_zones" and "zone" in want)}
+
     # Connectivity classes (cyc_table_classes / cyc_table_cells_at), cell by cell: the pods grouped by the bytes of their
     # row (as sources) or column (as destinations) of the view's cell codes, numbered by first occurrence.
     def classes(self, view="combined", k_lo=0, k_hi=None, want=("src", "dst"), hash_mask=None, stats=False):
@@ -661,6 +688,39 @@ class Table:
         seeds = [self.index[p] for p in ([pods] if isinstance(pods, str) else pods)]
         hops = self.src.reach([seeds], direction, self.slots.start, self.slots.stop, max_hops, want=("hops",))["hops"][0]
         return {p.pod_string(): int(hops[i]) for i, p in enumerate(self.resources.pods) if hops[i] >= 0}
+
+    # All pairs through any number of hops: the zones (pods that all reach one another) and how far every pod gets.
+    def _zones(self):
+        z = self.src.zones(self.slots.start, self.slots.stop, want=("zone",))
+        members = [[] for _ in range(z["n_zones"])]
+        for p, x in enumerate(z["zone"].tolist()):
+            members[x].append(p)
+        return members
+
+    def zones(self) -> dict:
+        """{"zones": [[pods of zone 0], ...]}: the pods ("ns/name", in plane order) that all reach one another over edges
+        that are a Combined of allowed in some slot of the table, whatever the number of hops; zones in the order of their
+        first pod; found by the cells source (cyc_table_zones on the device for a DeviceTable)."""
+        pods = self.resources.pods
+        return {"zones": [[pods[p].pod_string() for p in z] for z in self._zones()]}
+
+    def blast_radius(self) -> dict:
+        """{pod: (reaches, reached_by)}: the number of pods the pod gets to through any number of hops and the number
+        that get to it, each with the pod itself."""
+        z = self.src.zones(self.slots.start, self.slots.stop, want=("n_from", "n_to"))
+        return {p.pod_string(): (int(z["n_from"][i]), int(z["n_to"][i])) for i, p in enumerate(self.resources.pods)}
+
+    def render_zone_table(self) -> str:
+        """Zones by zones, each labelled by its first pod and " (+N)" for its N other members; a cell is "X" where the
+        pods of the row's zone reach the pods of the column's zone, "." where they do not (read off the closure rows of
+        the zones' first pods)."""
+        m, pods = self._zones(), self.resources.pods
+        label = lambda z: pods[z[0]].pod_string() + (f" (+{len(z) - 1})" if len(z) > 1 else "")  # noqa: E731
+        heads = [z[0] for z in m]
+        rows = self.src.closure("from", self.slots.start, self.slots.stop, want=("plane",))["plane"][heads]
+        rows = (rows.cpu().numpy() if hasattr(rows, "cpu") else np.asarray(rows)).view(np.uint64).reshape(len(heads), -1)
+        cell = lambda i, q: "X" if (int(rows[i, q // 64]) >> (q % 64)) & 1 else "."  # noqa: E731
+        return render([""] + [label(z) for z in m], [[label(z)] + [cell(i, q) for q in heads] for i, z in enumerate(m)], row_line=False)
 
     # The lossless summary: the pods that behave alike, and the table of one representative per class.
     def _classes(self, view):

@@ -510,6 +510,39 @@ int cyc_table_adjacency(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction 
 int cyc_table_reach(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction /* cyc_reach_direction */,
                     const int64_t* seed_off, const int32_t* seeds, int64_t n_sets, int64_t max_hops, uint64_t* reach,
                     int32_t* hops, int64_t* levels);
+/* ---- All pairs at once: the reflexive transitive closure of those edges, and the zones read off it (how far each
+ * pod gets, from how many pods it is reached, which pods all reach one another).  The reference has no such summary.
+ * Edges, accepted tables and their refusal text, stream, lifetime, failures and plane alignment as for
+ * cyc_table_reach; neither call changes the table, the context, its options or cyc_last_*.  Outputs are written only
+ * when the call succeeds; the results are exact and the same from run to run.  An unknown direction or a bad slot
+ * range: CYC_ERR_ARG.
+ *
+ * cyc_table_closure: row p of the closure is the `reach` row cyc_table_reach returns for the seed set {p} with the same
+ * slot range and direction and max_hops < 0:
+ *   CYC_REACH_FROM  row p, bit q set iff a path of >= 0 edges leads from p to q
+ *   CYC_REACH_TO    row p, bit q set iff such a path leads from q to p (the transpose)
+ * Bit p of row p is always set, a loopback edge changes nothing, bits at or beyond P are 0; an empty slot range gives
+ * the identity.  Outputs (each optional, at least one, or CYC_ERR_ARG):
+ *   d_closure  a DEVICE plane [P][W], 8-byte aligned (or CYC_ERR_ARG naming d_closure); exactly the plane's bytes are
+ *              written, synchronously on the table's stream like cyc_table_adjacency's d_adj
+ *   n_reach    host [P]: the set bits of row p (>= 1)
+ * With P == 0 nothing is written and the call returns CYC_OK.
+ * Device scratch of the call, freed before it returns: one closure plane of P rows of W words rounded up to 16, a pivot
+ * panel of 64 such rows, one 64-bit word per pod (two with n_reach) and, for CYC_REACH_FROM, 16 bytes per (slot, word)
+ * of the range; an allocation that fails is CYC_ERR_OOM with the byte count and what it was for.  The work is W steps
+ * of two launches over that plane (a blocked Warshall, 64 pivots a step). */
+int cyc_table_closure(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction /* cyc_reach_direction */,
+                      uint64_t* d_closure /* DEVICE [P][W], optional */, int64_t* n_reach /* host [P], optional */);
+/* The zones of the table: pods p and q are in one zone iff each reaches the other (the strongly connected components
+ * of the edges).  Zone ids are canonical like cyc_table_classes' class ids: zones are numbered 0, 1, ... in the order
+ * of their smallest member pod, so zone[0] == 0.  Outputs (host, each optional, at least one, or CYC_ERR_ARG):
+ *   zone     int32 [P]: the zone of every pod;  n_zones: the number of zones
+ *   n_from   [P]: the pods that p reaches, itself included (the CYC_REACH_FROM closure's row count)
+ *   n_to     [P]: the pods that reach p, itself included (its column count)
+ * An empty slot range gives zone[p] = p, n_zones = P and all counts 1; with P == 0 only n_zones (0) is written.
+ * Device scratch: cyc_table_closure's for CYC_REACH_FROM, and 20 bytes a pod. */
+int cyc_table_zones(cyc_table* t, int64_t k_lo, int64_t k_hi, int32_t* zone, int64_t* n_zones,
+                    int64_t* n_from /* host [P] */, int64_t* n_to /* host [P] */);
 /* ---- Connectivity classes: the lossless summary of a table.  The reference prints every pod (table.go:58-156);
  * most pods of a real cluster behave exactly like many others, and the whole table is a class x class table
  * (cyc_table_cells_at over one representative per class) plus the two index arrays below.  Unlike the engine's

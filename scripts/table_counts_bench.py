@@ -2,11 +2,12 @@
 
     python scripts/table_counts_bench.py time [reps=3] [out=FILE]   # the table below, as text and one JSON line
     python scripts/table_counts_bench.py run counts|compare|find_count|compare_find|find_dense|group_counts|group_compare|
-                                             pod_counts|pod_compare [n=2]   # n calls of one pass (for a rocprofv3 run)
+                                             pod_counts|pod_compare|closure [n=2]   # n calls of one pass (for a rocprofv3 run)
     python scripts/table_counts_bench.py group [reps=3] [out=FILE]  # the group leg alone (below)
     python scripts/table_counts_bench.py pod [reps=3] [out=FILE]    # the pod leg alone (below)
     python scripts/table_counts_bench.py reach [reps=3] [out=FILE]  # the reachability leg alone (below)
     python scripts/table_counts_bench.py classes [reps=3] [out=FILE]  # the connectivity-class leg alone (below)
+    python scripts/table_counts_bench.py closure [reps=3] [out=FILE]  # the transitive-closure leg alone (below)
 
 In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
 drawn with another seed; then, min over reps of the synchronous calls,
@@ -41,6 +42,12 @@ plain read, min over reps of each:
   classes   cyc_table_classes_masked with stats for sources only, destinations only and both; the numbers of classes,
             the verification rounds and the pods that failed one
   cells_at  cyc_table_cells_at over one representative per class (the class table)
+The closure leg (mode `closure`): every slot, interleaved with counts, the adjacency pass and one cyc_table_reach of 64
+single-pod seed sets, min over reps of each:
+  closure   cyc_table_closure into a device plane with n_reach, both directions
+  zones     cyc_table_zones, all outputs; the number of zones and the largest one
+and the closure against the only other way to all rows, P / 64 reach calls of 64 sets.  The split between the panel
+and the update launches comes from a rocprofv3 --kernel-trace --stats run of `run closure`.
 """
 import json
 import os
@@ -135,7 +142,8 @@ LISTINGS = {
 }
 
 if mode == "run":
-    f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS, **GROUP, **POD}[pos[0]]
+    f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS, **GROUP, **POD,
+         "closure": lambda: ta.closure(want=("n_reach",))}[pos[0]]
     for _ in range(n_run):
         f()
     sys.exit(0)
@@ -270,6 +278,56 @@ if mode == "reach":
             f"per set, deepest level {int(g['levels'].max())}; rows gathered {bound_gb:.2f} GB (bound {res[f'reach{n}_bound_gb']:.2f} GB: the plane once per set), "
             f"{bound_gb / max(step_ms, 1e-9) * 1e3:.0f} GB/s over the steps; device scratch {scratch_mb:.0f} MB")
     lines.append(json.dumps(res))
+    print("\n".join(lines))
+    if "out" in kw:
+        os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
+        with open(kw["out"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
+
+if mode == "closure":
+    # slots [0, K): the closure both ways into a device plane with the row counts, the zones, next to counts, the adjacency
+    # pass and one search from 64 single-pod seed sets: P / 64 such calls are the other way to every row of the closure.
+    rng = np.random.default_rng(16)
+    seeds = [[int(p)] for p in rng.integers(0, P, 64)]
+    plane = torch.empty((P, W), dtype=torch.int64, device="cuda")
+    pitch = (W + 15) // 16 * 16
+    legs = {"counts": lambda: ta.counts(), "adjacency_from": lambda: ta.adjacency("from", d_out=plane.data_ptr()),
+            "reach64": lambda: ta.reach(seeds, want=("reach",)),
+            "closure_from": lambda: ta.closure("from", d_out=plane.data_ptr()), "closure_to": lambda: ta.closure("to", d_out=plane.data_ptr()),
+            "zones": lambda: ta.zones()}
+    z = ta.zones()  # (warm-up, and the figures)
+    n_from = ta.closure("from", want=("n_reach",))["n_reach"]
+    assert np.array_equal(n_from, z["n_from"])
+    # a sample of the closure's rows against the search: the rows of the 64 seed pods
+    rows = ta.closure("from", want=("plane",))["plane"][[s[0] for s in seeds]].cpu().numpy().view(np.uint64)
+    assert np.array_equal(rows, ta.reach(seeds, want=("reach",))["reach"]), "closure rows differ from cyc_table_reach"
+    for f in legs.values():
+        f()
+    ms = {n: float("inf") for n in legs}
+    for _ in range(reps):  # interleaved: every leg once per round
+        for n, f in legs.items():
+            ms[n] = min(ms[n], timed(f, 1))
+    sizes = np.bincount(z["zone"])
+    scratch_mb = (P * pitch * 8 + 64 * pitch * 8 + 2 * P * 8 + K * W * 16) / 1e6
+    route_ms = (P + 63) // 64 * ms["reach64"]
+    res = {"config": config, "pods": P, "slots": K, "words": W, "plane_gb": round(plane_gb, 3), "reps": reps,
+           **{n + "_ms": v for n, v in ms.items()}, "closure_gb": P * W * 8 / 1e9, "n_zones": z["n_zones"], "largest_zone": int(sizes.max()),
+           "zones_of_one": int((sizes == 1).sum()), "mean_reach": float(z["n_from"].mean()), "max_reach": int(z["n_from"].max()),
+           "closure_bits": int(z["n_from"].sum()), "scratch_mb": scratch_mb, "launches": 2 * W, "reach_route_ms": route_ms,
+           "closure_over_reach_route": ms["closure_from"] / route_ms, "update_bound_gb_per_pivot_word": 2 * P * pitch * 8 / 1e9}
+    lines = [
+        f"# {config}: P {P}, K {K}, W {W}, slots [0, {K}); a plane is {plane_gb:.2f} GB, the closure plane {res['closure_gb']:.3f} GB; "
+        f"min of {reps} interleaved synchronous calls",
+        f"counts {ms['counts']:9.2f} ms   adjacency from {ms['adjacency_from']:9.2f} ms   reach from 64 single-pod sets {ms['reach64']:9.2f} ms",
+        f"closure from {ms['closure_from']:9.2f} ms   to {ms['closure_to']:9.2f} ms ({2 * W} launches of the pivot steps)   zones {ms['zones']:9.2f} ms   "
+        f"device scratch {scratch_mb:.0f} MB",
+        f"{z['n_zones']} zones of {P} pods, the largest {int(sizes.max())} pods, {res['zones_of_one']} of one pod; a pod reaches {res['mean_reach']:.1f} pods "
+        f"on average, at most {res['max_reach']}; {res['closure_bits']} bits of the closure set ({res['closure_bits'] / P / P * 100:.2f} %)",
+        f"every row by reach: {(P + 63) // 64} calls of 64 sets x {ms['reach64']:.2f} ms = {route_ms / 1e3:.2f} s; the closure takes "
+        f"{res['closure_over_reach_route'] * 100:.2f} % of that ({'less' if ms['closure_from'] < route_ms else 'NOT less'} than the reach route)",
+        json.dumps(res),
+    ]
     print("\n".join(lines))
     if "out" in kw:
         os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
