@@ -66,6 +66,7 @@ EXPORTS = [
     "cyc_table_reach",
     "cyc_table_closure",
     "cyc_table_zones",
+    "cyc_table_zone_graph",
     "cyc_table_classes",
     "cyc_table_classes_masked",
     "cyc_table_cells_at",
@@ -243,6 +244,7 @@ def lib():
         L.cyc_table_reach.argtypes = [vp, i64, i64, i, vp, vp, i64, i64, vp, vp, vp]
         L.cyc_table_closure.argtypes = [vp, i64, i64, i, vp, vp]
         L.cyc_table_zones.argtypes = [vp, i64, i64, vp, vp, vp, vp]
+        L.cyc_table_zone_graph.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64]
         L.cyc_table_classes.argtypes = [vp, i, i64, i64, vp, vp, vp, vp]
         L.cyc_table_classes_masked.argtypes = [vp, i, i64, i64, vp, vp, vp, vp, ctypes.c_uint64, vp]
         L.cyc_table_cells_at.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp]

@@ -3,7 +3,7 @@
     python -m cyclonus_amd.build        # or __graft_entry__.build()
 
 host.cpp (policy compiler, probe model, table flattening) is compiled with g++; engine.hip
-(kernels + C ABI, with its stage headers dev_*.hpp / route / ctx / plan / enqueue / effects / table / reach / closure / classes.hpp as one translation
+(kernels + C ABI, with its stage headers dev_*.hpp / route / ctx / plan / enqueue / effects / table / reach / closure / zone_graph / classes.hpp as one translation
 unit) with hipcc --offload-arch=gfx950; both are linked by hipcc into one shared
 library with plain C entry points declared in include/cyclonus_hip.h.
 """
@@ -26,8 +26,8 @@ SOURCES_CPP = ["host.cpp"]
 SOURCES_HIP = ["engine.hip"]
 # engine.hip's stage headers (one translation unit) and the host headers
 HEADERS = ["cjson.hpp", "host.hpp", "tables.h", "route.hpp", "dev_select.hpp", "dev_peer_rows.hpp", "dev_slots.hpp", "dev_member.hpp",
-           "dev_class_rows.hpp", "dev_front.hpp", "dev_emit.hpp", "dev_query.hpp", "dev_gather.hpp", "dev_table.hpp", "dev_effects.hpp", "dev_reach.hpp", "dev_closure.hpp", "dev_classes.hpp", "ctx.hpp", "plan.hpp",
-           "enqueue.hpp", "effects.hpp", "table_terms.hpp", "table.hpp", "reach_terms.hpp", "reach.hpp", "closure_terms.hpp", "closure.hpp", "class_terms.hpp", "classes.hpp", "comm.hpp"]
+           "dev_class_rows.hpp", "dev_front.hpp", "dev_emit.hpp", "dev_query.hpp", "dev_gather.hpp", "dev_table.hpp", "dev_effects.hpp", "dev_reach.hpp", "dev_closure.hpp", "dev_zone_graph.hpp", "dev_classes.hpp", "ctx.hpp", "plan.hpp",
+           "enqueue.hpp", "effects.hpp", "table_terms.hpp", "table.hpp", "reach_terms.hpp", "reach.hpp", "closure_terms.hpp", "closure.hpp", "zone_terms.hpp", "zone_graph.hpp", "class_terms.hpp", "classes.hpp", "comm.hpp"]
 LIBS = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]  # RCCL: the table assembly's all-gathers (comm.hpp)
 
 

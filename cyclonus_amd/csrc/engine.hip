@@ -61,9 +61,10 @@
 #include "dev_effects.hpp"
 #include "dev_reach.hpp"
 #include "dev_closure.hpp"
+#include "dev_zone_graph.hpp"
 #include "dev_classes.hpp"
 
-// Host side: context, planner, enqueueing, the bodies of the effects, table, reach, closure and class calls; the C ABI below
+// Host side: context, planner, enqueueing, the bodies of the effects, table, reach, closure, zone graph and class calls; the C ABI below
 #include "ctx.hpp"
 #include "plan.hpp"
 #include "enqueue.hpp"
@@ -71,6 +72,7 @@
 #include "table.hpp"
 #include "reach.hpp"
 #include "closure.hpp"
+#include "zone_graph.hpp"
 #include "classes.hpp"
 
 extern "C" {
@@ -534,6 +536,11 @@ int cyc_table_closure(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction, u
 
 int cyc_table_zones(cyc_table* t, int64_t k_lo, int64_t k_hi, int32_t* zone, int64_t* n_zones, int64_t* n_from, int64_t* n_to) {
   return t ? table_zones(t, k_lo, k_hi, zone, n_zones, n_from, n_to) : (int)CYC_ERR_ARG;
+}
+
+int cyc_table_zone_graph(cyc_table* t, int64_t k_lo, int64_t k_hi, int32_t* zone, int64_t* n_zones, int32_t* rep, int64_t* size, int32_t* tier,
+                         cyc_zone_edge* edges, int64_t edge_cap, int64_t* n_edges, uint64_t* d_zreach, int64_t zreach_words) {
+  return t ? table_zone_graph(t, k_lo, k_hi, zone, n_zones, rep, size, tier, edges, edge_cap, n_edges, d_zreach, zreach_words) : (int)CYC_ERR_ARG;
 }
 
 int cyc_table_classes(cyc_table* t, int view, int64_t k_lo, int64_t k_hi, int32_t* src_class, int32_t* dst_class, int64_t* n_src, int64_t* n_dst) {

@@ -572,6 +572,57 @@ class DeviceTable:
             out["n_zones"] = int(nz.value)
         return out
 
+    # ---- how the zones are connected (cyc_table_zone_graph)
+    def zone_graph(self, k_lo=0, k_hi=None, want=("zone", "rep", "size", "tier", "edges"), max_zones=None, max_edges=None):
+        """cyc_table_zone_graph: the condensation of the reach graph reduced to its cover edges: {"zone": i32 [P] as
+        zones(), "n_zones": int Z, "rep": i32 [Z] the smallest pod of every zone, "size": i64 [Z] its pods, "tier": i32 [Z]
+        the edges of the longest chain of cover edges that ends in it, "edges": i32 [n, 2] the cover edges (a, b) in
+        ascending order (a reaches b and no third zone lies between them), "n_edges": int}.  The edges take a count-only
+        call first, then the listing.  "reach" (on request): the reflexive zone reach matrix as a bit plane
+        [Z, ceil(Z / 64)] on the table's device (a torch int64 tensor).  With max_zones (an upper bound of Z, the pods at
+        the most) the plane is allocated for that many zones and costs no call of its own; without it a first call
+        learns Z, which costs a second closure.  Likewise max_edges (an upper bound of the number of edges, from an
+        earlier call on the same table and slots) lists the edges without the count-only call; one that is too small is the
+        library's capacity error.  With the bounds that apply the whole result is one call."""
+        k_hi = self.slots if k_hi is None else k_hi
+        P = self.pods
+        dt = {"zone": np.int32, "rep": np.int32, "size": np.int64, "tier": np.int32}
+        out = {x: np.zeros(P, dt[x]) for x in want if x in dt}
+        nz, ne = ctypes.c_int64(0), ctypes.c_int64(0)
+        # (empty numpy arrays still have a data pointer: an empty output is never the NULL the library refuses)
+        p = [ctypes.c_void_p(out[x].ctypes.data) if x in out else None for x in ("zone", "rep", "size", "tier")]
+
+        def call(outs, edges, cap, plane, words):
+            self._check(lib().cyc_table_zone_graph(self._t, int(k_lo), int(k_hi), outs[0], ctypes.byref(nz), *outs[1:], edges, cap,
+                                                   ctypes.byref(ne), plane, words))
+
+        none = [None] * 4
+        edges, plane = None, None
+        if ("edges" in want and max_edges is None) or ("reach" in want and max_zones is None):
+            call(none, None, 0, None, 0)  # the counts: Z and the number of edges
+        if "edges" in want:
+            edges = np.zeros((int(ne.value) if max_edges is None else int(max_edges), 2), np.int32)
+        if "reach" in want:
+            import torch
+
+            zmax = int(nz.value) if max_zones is None else int(max_zones)
+            plane = torch.zeros(zmax * ((zmax + 63) // 64), dtype=torch.int64, device=f"cuda:{self.device}")
+        if out or plane is not None or edges is not None:
+            call(p, ctypes.c_void_p(edges.ctypes.data) if "edges" in want else None, len(edges) if "edges" in want else 0,
+                 ctypes.c_void_p(plane.data_ptr()) if plane is not None and plane.numel() else None, plane.numel() if plane is not None else 0)
+        else:
+            call(none, None, 0, None, 0)
+        Z = int(nz.value)
+        for x in ("rep", "size", "tier"):
+            if x in out:
+                out[x] = out[x][:Z].copy()
+        if "edges" in want:
+            out["edges"] = edges[:int(ne.value)]
+        if plane is not None:
+            out["reach"] = plane[:Z * ((Z + 63) // 64)].view(Z, (Z + 63) // 64)
+        out["n_zones"], out["n_edges"] = Z, int(ne.value)
+        return out
+
     # ---- connectivity classes (cyc_table_classes, cyc_table_cells_at)
     def classes(self, view="combined", k_lo=0, k_hi=None, want=("src", "dst"), hash_mask=None, stats=False):
         """cyc_table_classes: the pods partitioned by equal rows ("src") and equal columns ("dst") of `view`'s cell codes

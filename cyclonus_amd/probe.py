@@ -518,6 +518,32 @@ class PlaneCells:
                "n_from": m.sum(axis=1, dtype=np.int64), "n_to": m.sum(axis=0, dtype=np.int64)}
         return {x: out[x] for x in out if x in want or (x == "n_zones" and "zone" in want)}
 
+    def zone_graph(self, k_lo=0, k_hi=None, want=("zone", "rep", "size", "tier", "edges"), max_zones=None, max_edges=None):
+        """cyc_table_zone_graph: {"zone": i32 [P], "n_zones": int, "rep": i32 [Z], "size": i64 [Z], "tier": i32 [Z],
+        "edges": i32 [n, 2], "n_edges": int, "reach": u64 [Z, ceil(Z / 64)]} (DeviceTable.zone_graph; max_zones and
+        max_edges belong to the device and are ignored).  The cover edges by a matrix product over the unpacked zone matrix: small P only."""
+        P = self.status.shape[0]
+        c = self.closure("from", k_lo, k_hi, want=("plane",))["plane"]
+        zone = self.zones(k_lo, k_hi, want=("zone",))["zone"]
+        m = np.unpackbits(c.view(np.uint8), axis=1, bitorder="little")[:, :P].astype(bool).reshape(P, P)
+        heads = np.unique(zone, return_index=True)[1]  # the first pod of every zone, in the order of the zone ids
+        Z = len(heads)
+        R = m[heads][:, heads]
+        S = R & ~np.eye(Z, dtype=bool)
+        cover = S & ~((S.astype(np.int32) @ S.astype(np.int32)) > 0)
+        # the number of zones that reach a zone orders a strict partial order topologically: tiers by relaxing in it
+        tier = np.zeros(Z, np.int32)
+        for b in np.argsort(S.sum(axis=0), kind="stable"):
+            into = np.flatnonzero(cover[:, b])
+            if len(into):
+                tier[b] = tier[into].max() + 1
+        bits = np.zeros((Z, (Z + 63) // 64 * 64), np.uint8)
+        bits[:, :Z] = R
+        out = {"zone": zone, "n_zones": Z, "rep": heads.astype(np.int32), "size": np.bincount(zone, minlength=Z).astype(np.int64),
+               "tier": tier, "edges": np.argwhere(cover).astype(np.int32).reshape(-1, 2), "n_edges": int(cover.sum()),
+               "reach": np.packbits(bits, axis=1, bitorder="little").view(np.uint64).reshape(Z, (Z + 63) // 64)}
+        return {x: out[x] for x in out if x in want or x in ("n_zones", "n_edges")}
+
     # Connectivity classes (cyc_table_classes / cyc_table_cells_at), cell by cell: the pods grouped by the bytes of their
     # row (as sources) or column (as destinations) of the view's cell codes, numbered by first occurrence.
     def classes(self, view="combined", k_lo=0, k_hi=None, want=("src", "dst"), hash_mask=None, stats=False):
@@ -721,6 +747,43 @@ class Table:
         rows = (rows.cpu().numpy() if hasattr(rows, "cpu") else np.asarray(rows)).view(np.uint64).reshape(len(heads), -1)
         cell = lambda i, q: "X" if (int(rows[i, q // 64]) >> (q % 64)) & 1 else "."  # noqa: E731
         return render([""] + [label(z) for z in m], [[label(z)] + [cell(i, q) for q in heads] for i, z in enumerate(m)], row_line=False)
+
+    # How the zones are connected: the cover edges between them (a -> b with no third zone between) and their tiers.
+    def _zone_graph(self):
+        g = self.src.zone_graph(self.slots.start, self.slots.stop, want=("zone", "tier", "edges"))
+        members = [[] for _ in range(g["n_zones"])]
+        for p, x in enumerate(g["zone"].tolist()):
+            members[x].append(p)
+        return members, g["tier"].tolist(), g["edges"].tolist()
+
+    def zone_graph(self) -> dict:
+        """{"zones": [[pods of zone 0], ...], "tiers": [tier of zone 0, ...], "edges": [[a, b], ...]}: zones() with the
+        zone ids of the cover edges (zone a reaches zone b and no third zone lies between them; every other connection
+        between zones follows from these) in ascending order, and per zone the edges of the longest chain of cover edges
+        that ends in it (0: no other zone reaches it); found by the cells source (cyc_table_zone_graph on the device for
+        a DeviceTable)."""
+        m, tiers, edges = self._zone_graph()
+        pods = self.resources.pods
+        return {"zones": [[pods[p].pod_string() for p in z] for z in m], "tiers": tiers, "edges": edges}
+
+    def render_zone_graph(self, fmt: str = "text") -> str:
+        """The zone graph as text (the zones grouped by tier, then a line "a -> b" per cover edge) or as a Graphviz
+        digraph ("dot": a rank=same group per tier); zones labelled like render_zone_table's."""
+        if fmt not in ("text", "dot"):
+            raise ValueError(f"invalid format: {fmt}")
+        m, tiers, edges = self._zone_graph()
+        pods = self.resources.pods
+        label = [pods[z[0]].pod_string() + (f" (+{len(z) - 1})" if len(z) > 1 else "") for z in m]
+        by_tier = [[z for z in range(len(m)) if tiers[z] == t] for t in range(max(tiers, default=-1) + 1)]
+        if fmt == "text":
+            out = [f"tier {t}: " + ", ".join(label[z] for z in zs) for t, zs in enumerate(by_tier)]
+            out += [f"{label[a]} -> {label[b]}" for a, b in edges]
+            return "\n".join(out) + "\n"
+        out = ["digraph zones {"]
+        out += [f'  z{z} [label="{label[z]}"];' for z in range(len(m))]
+        out += ["  { rank=same; " + " ".join(f"z{z};" for z in zs) + " }" for zs in by_tier]
+        out += [f"  z{a} -> z{b};" for a, b in edges]
+        return "\n".join(out + ["}"]) + "\n"
 
     # The lossless summary: the pods that behave alike, and the table of one representative per class.
     def _classes(self, view):

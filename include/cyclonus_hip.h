@@ -543,6 +543,45 @@ int cyc_table_closure(cyc_table* t, int64_t k_lo, int64_t k_hi, int direction /*
  * Device scratch: cyc_table_closure's for CYC_REACH_FROM, and 20 bytes a pod. */
 int cyc_table_zones(cyc_table* t, int64_t k_lo, int64_t k_hi, int32_t* zone, int64_t* n_zones,
                     int64_t* n_from /* host [P] */, int64_t* n_to /* host [P] */);
+/* ---- How the zones are connected: the condensation of the reach graph (one node per zone) reduced to its Hasse
+ * diagram, and the tier of every zone.  The reference has no such summary.  Edges, slot range, accepted tables and
+ * their refusal text, stream, lifetime and plane alignment as for cyc_table_zones; nothing about the table, its
+ * context, the options or cyc_last_* changes; the results are exact and the same from run to run.
+ *
+ * Z and the zone numbering are cyc_table_zones' (canonical by smallest member pod), so rep is ascending and
+ * rep[0] == 0.  Zone a reaches zone b iff rep[a] reaches rep[b] in the CYC_REACH_FROM closure (reflexive); the strict
+ * relation S drops the diagonal and is a strict partial order.  a -> b is a cover edge iff S[a][b] and no zone c has
+ * S[a][c] and S[c][b].  Every cover edge is witnessed by a table edge from some pod of a to some pod of b; every other
+ * edge between two zones is a shortcut the cover edges imply.  tier[z] is the number of edges of the longest chain of
+ * cover edges that ends in z: 0 for a zone that no other zone reaches.
+ *   zone      host int32 [P], optional: as cyc_table_zones;  n_zones: required, Z
+ *   rep       host int32, room for P, optional: [z] = the smallest pod of zone z (the first Z are written)
+ *   size      host int64, room for P, optional: [z] = the pods of zone z
+ *   tier      host int32, room for P, optional
+ *   edges     the cover edges in ascending (a, b) order.  *n_edges, when non-NULL, always receives their number.
+ *             edges == NULL with edge_cap == 0 is a count-only call.  edges non-NULL with edge_cap below the number is
+ *             CYC_ERR_ARG naming the number: *n_zones and *n_edges are set and nothing else is written.  edges without
+ *             n_edges, a negative edge_cap, or NULL edges with edge_cap > 0: CYC_ERR_ARG.
+ *   d_zreach  a DEVICE plane, optional: the reflexive zone reach matrix as tight rows [Z][Wz], Wz = ceil(Z / 64): row a
+ *             bit b set iff a reaches b, bits at or beyond Z are 0.  8-byte aligned (or CYC_ERR_ARG naming d_zreach);
+ *             exactly Z * Wz words are written, synchronously on the table's stream.  zreach_words < Z * Wz is
+ *             CYC_ERR_ARG naming Z and the words needed: *n_zones is set and nothing else is written.
+ * Apart from those two capacity failures outputs are written only on success.  An empty slot range gives Z = P,
+ * zone[p] = rep[p] = p, sizes 1, tiers 0, no edge and the identity plane; with P == 0 only *n_zones = 0 and
+ * *n_edges = 0 are written.  A NULL n_zones is CYC_ERR_ARG; a bad slot range or a partial table fails with
+ * cyc_table_zones' messages.
+ * Device scratch: cyc_table_zones', 4 bytes a zone, and as far as the outputs need them: the zone reach plane of Z
+ * rows of Wz words rounded up to 16 (edges, tiers or d_zreach), a second such plane and 8 bytes a zone (edges or
+ * tiers), 8 bytes an edge (a listing).  An allocation that fails is CYC_ERR_OOM with the byte count and what it was
+ * for.  The work beyond cyc_table_zones' is a gather of the closure into the zone plane and one boolean product over it
+ * in a single launch. */
+typedef struct {
+  int32_t a, b; /* zone a -> zone b, a != b */
+} cyc_zone_edge;
+int cyc_table_zone_graph(cyc_table* t, int64_t k_lo, int64_t k_hi, int32_t* zone /* host [P], optional */,
+                         int64_t* n_zones, int32_t* rep, int64_t* size, int32_t* tier, cyc_zone_edge* edges,
+                         int64_t edge_cap, int64_t* n_edges, uint64_t* d_zreach /* DEVICE, optional */,
+                         int64_t zreach_words);
 /* ---- Connectivity classes: the lossless summary of a table.  The reference prints every pod (table.go:58-156);
  * most pods of a real cluster behave exactly like many others, and the whole table is a class x class table
  * (cyc_table_cells_at over one representative per class) plus the two index arrays below.  Unlike the engine's

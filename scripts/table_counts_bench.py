@@ -2,12 +2,13 @@
 
     python scripts/table_counts_bench.py time [reps=3] [out=FILE]   # the table below, as text and one JSON line
     python scripts/table_counts_bench.py run counts|compare|find_count|compare_find|find_dense|group_counts|group_compare|
-                                             pod_counts|pod_compare|closure [n=2]   # n calls of one pass (for a rocprofv3 run)
+                                             pod_counts|pod_compare|closure|zone_graph [n=2]   # n calls of one pass (for a rocprofv3 run)
     python scripts/table_counts_bench.py group [reps=3] [out=FILE]  # the group leg alone (below)
     python scripts/table_counts_bench.py pod [reps=3] [out=FILE]    # the pod leg alone (below)
     python scripts/table_counts_bench.py reach [reps=3] [out=FILE]  # the reachability leg alone (below)
     python scripts/table_counts_bench.py classes [reps=3] [out=FILE]  # the connectivity-class leg alone (below)
     python scripts/table_counts_bench.py closure [reps=3] [out=FILE]  # the transitive-closure leg alone (below)
+    python scripts/table_counts_bench.py zone_graph [reps=3] [out=FILE]  # the zone graph leg alone (below)
 
 In one process: the table of config #3 (2 x 10 GB planes) and a second table of the same pods under policies
 drawn with another seed; then, min over reps of the synchronous calls,
@@ -48,6 +49,11 @@ single-pod seed sets, min over reps of each:
   zones     cyc_table_zones, all outputs; the number of zones and the largest one
 and the closure against the only other way to all rows, P / 64 reach calls of 64 sets.  The split between the panel
 and the update launches comes from a rocprofv3 --kernel-trace --stats run of `run closure`.
+The zone graph leg (mode `zone_graph`): every slot, interleaved with cyc_table_zones, min over reps of each:
+  zone_graph  cyc_table_zone_graph, every output and the zone reach plane in one call (the bounds from a count-only call
+              made once); the count-only call; the unbounded form of the Python mirror (two calls, two closures)
+and the number of zones, the cover edges against the set bits of the strict zone reach matrix, the tiers.  The split
+between the compress, cover and listing launches comes from a rocprofv3 --kernel-trace --stats run of `run zone_graph`.
 """
 import json
 import os
@@ -141,9 +147,20 @@ LISTINGS = {
     "find_dense": lambda: ta.find("combined", (CONN_ALLOWED,), out=page),
 }
 
+ZG_ALL = ("zone", "rep", "size", "tier", "edges", "reach")
+
+
+def zone_graph_single_pass():
+    """Every output of cyc_table_zone_graph in one call: the bounds come from a count-only call made once."""
+    if not hasattr(zone_graph_single_pass, "bounds"):
+        c = ta.zone_graph(want=())
+        zone_graph_single_pass.bounds = {"max_zones": c["n_zones"], "max_edges": c["n_edges"]}
+    return ta.zone_graph(want=ZG_ALL, **zone_graph_single_pass.bounds)
+
+
 if mode == "run":
     f = {"counts": lambda: ta.counts(), "compare": lambda: ta.compare(tb, d_diff=diff.data_ptr()), **LISTINGS, **GROUP, **POD,
-         "closure": lambda: ta.closure(want=("n_reach",))}[pos[0]]
+         "closure": lambda: ta.closure(want=("n_reach",)), "zone_graph": zone_graph_single_pass}[pos[0]]
     for _ in range(n_run):
         f()
     sys.exit(0)
@@ -326,6 +343,45 @@ if mode == "closure":
         f"on average, at most {res['max_reach']}; {res['closure_bits']} bits of the closure set ({res['closure_bits'] / P / P * 100:.2f} %)",
         f"every row by reach: {(P + 63) // 64} calls of 64 sets x {ms['reach64']:.2f} ms = {route_ms / 1e3:.2f} s; the closure takes "
         f"{res['closure_over_reach_route'] * 100:.2f} % of that ({'less' if ms['closure_from'] < route_ms else 'NOT less'} than the reach route)",
+        json.dumps(res),
+    ]
+    print("\n".join(lines))
+    if "out" in kw:
+        os.makedirs(os.path.dirname(os.path.abspath(kw["out"])), exist_ok=True)
+        with open(kw["out"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
+
+if mode == "zone_graph":
+    # slots [0, K): cyc_table_zone_graph with every output in one call (the bounds known) and as the Python mirror makes it
+    # without bounds (a count-only call, then the listing: two closures), interleaved with cyc_table_zones, its yardstick.
+    legs = {"zones": lambda: ta.zones(), "zone_graph": zone_graph_single_pass, "zone_graph_count_only": lambda: ta.zone_graph(want=()),
+            "zone_graph_unbounded": lambda: ta.zone_graph(want=ZG_ALL)}
+    z, g = ta.zones(), zone_graph_single_pass()  # (warm-up, and the figures)
+    assert np.array_equal(g["zone"], z["zone"]) and g["n_zones"] == z["n_zones"]
+    for f in legs.values():
+        f()
+    ms = {n: float("inf") for n in legs}
+    for _ in range(reps):  # interleaved: every leg once per round
+        for n, f in legs.items():
+            ms[n] = min(ms[n], timed(f, 1))
+    Z, E = g["n_zones"], g["n_edges"]
+    Wz = (Z + 63) // 64
+    zpitch = (Wz + 15) // 16 * 16
+    strict = int(np.unpackbits(g["reach"].cpu().numpy().view(np.uint8)).sum()) - Z  # the set bits of the zone reach plane without its diagonal
+    tiers = np.bincount(g["tier"])
+    scratch_mb = (2 * Z * zpitch * 8 + Z * 12 + E * 8) / 1e6
+    res = {"config": config, "pods": P, "slots": K, "words": W, "reps": reps, **{n + "_ms": v for n, v in ms.items()}, "n_zones": Z, "zone_words": Wz,
+           "cover_edges": E, "strict_reach_bits": strict, "tiers": len(tiers), "widest_tier": int(tiers.max()), "widest_tier_at": int(tiers.argmax()),
+           "largest_zone": int(g["size"].max()), "zone_graph_over_zones": ms["zone_graph"] / ms["zones"], "extra_scratch_mb": scratch_mb}
+    lines = [
+        f"# {config}: P {P}, K {K}, W {W}, slots [0, {K}); min of {reps} interleaved synchronous calls",
+        f"zones {ms['zones']:9.2f} ms   zone_graph, every output in one call {ms['zone_graph']:9.2f} ms   ratio {res['zone_graph_over_zones']:.3f} "
+        f"({'less' if res['zone_graph_over_zones'] < 2 else 'NOT less'} than twice zones)",
+        f"zone_graph count-only {ms['zone_graph_count_only']:9.2f} ms   count-only and listing, two closures {ms['zone_graph_unbounded']:9.2f} ms",
+        f"{Z} zones of {P} pods ({Wz} words a row of the zone plane), the largest {res['largest_zone']} pods; {E} cover edges of {strict} strict reach bits "
+        f"({E / max(strict, 1) * 100:.3f} %: the reduction removes {strict - E}); {len(tiers)} tiers, the widest tier {int(tiers.argmax())} with {int(tiers.max())} zones; "
+        f"device scratch beyond zones' {scratch_mb:.1f} MB",
         json.dumps(res),
     ]
     print("\n".join(lines))
